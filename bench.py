@@ -24,10 +24,24 @@ process (before anything touches a GPU) and prints rank 0's line:
   collective and per-GPU work is fixed, so scaling is "weak".
 
 Prints ONE JSON line on rank 0. `value` = G ray-march-steps/s of the whole job
-(primary + shadow march() iterations, counted exactly by the kernel, / wall time).
+(primary + shadow march() iterations, counted exactly by the kernel, / wall time);
+`ms_per_step` = wall milliseconds per timed frame (--steps of them, exactly).
+
+A plain run sets up, renders the warmup frames, times the --steps frames and prints the line
+(the roofline's achieved figure comes from that same timed region and its counters). Everything
+else is behind --full: the golden-frame hash and work-counter checks against the oracle's
+goldens, the committed PMC summary, the drop-in loops (and their child process at 4 hardware
+queues) and the CPU baseline.
+
+--dump-outputs DIR writes what the timed path handed its caller in its last step, after the
+timed region: DIR/frame.npy (the last timed frame's RGBA8 pixels as float32 [n, 4]; frames of
+more than 2^21 pixels as a fixed, seeded sample of 2^21 pixels in ascending pixel order) and
+DIR/counters.npy (the kernel's work counters summed over the timed frames, float64). Inputs are
+deterministic Parameters, so two builds run with the same arguments compare output for output.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload HEADLINE|HEADLINE_FLY|C2|C3|C4|C5]
-                    [--pose P0|P1|P2] [--kernel persistent|simple] [--no-cpu-baseline]
+                    [--pose P0|P1|P2] [--kernel persistent|simple] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-dropin]]
 """
 import argparse
 import hashlib
@@ -86,8 +100,17 @@ def parse():
                     help="exact: the bit-exact frm builtins (the product default, the headline); hw: "
                     "FRM_FLAG_HW_MATH, the Mandelbulb on hardware transcendentals (opt-in, not bit-exact, "
                     "gated by tests/test_gpu_hw_math.py; a separate line, never the headline)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-dropin", action="store_true", help="skip the drop-in loop measurement (dropin_ms_per_frame)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline figure: the golden-frame hash and work-counter "
+                    "checks (exit 3 when the counters differ), the committed PMC summary in the roofline, the "
+                    "drop-in loops (one more in a child process at 4 hardware queues) and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed frames, write the last timed frame (DIR/frame.npy, float32 [n, 4] RGBA; "
+                    "above 2^21 pixels a fixed seeded sample of 2^21) and the timed region's summed work "
+                    "counters (DIR/counters.npy, float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-dropin", action="store_true",
+                    help="with --full: skip the drop-in loop measurement (dropin_ms_per_frame)")
     ap.add_argument("--dropin-only", action="store_true",
                     help="internal: only the drop-in loop (2 in flight, a frame of latency), one JSON line; "
                     "bench.py runs it as a child at HIP's default 4 hardware queues (dropin_q4)")
@@ -380,6 +403,26 @@ def counters_check(counters, workload, pose, frames, golden_path=GOLDEN):
             **({"counters_mismatch": bad} if bad else {})}
 
 
+DUMP_MAX_PIXELS = 1 << 21  # 2^21 pixels x 4 channels x float32 = 32 MiB
+DUMP_SEED = 18
+
+
+def dump_outputs(path, frame, counters):
+    """--dump-outputs: the last timed frame (flat RGBA8, host) as DIR/frame.npy, float32 [n, 4];
+    a frame of more than DUMP_MAX_PIXELS pixels as the same seeded sample of that many pixels in
+    every run (ascending pixel index, row-major). The timed region's summed work counters as
+    DIR/counters.npy, float64 (exact: they stay far below 2^53)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    px = np.ascontiguousarray(frame).reshape(-1, 4)
+    if len(px) > DUMP_MAX_PIXELS:
+        idx = np.random.default_rng(DUMP_SEED).choice(len(px), DUMP_MAX_PIXELS, replace=False)
+        px = px[np.sort(idx)]
+    np.save(os.path.join(path, "frame.npy"), px.astype(np.float32))
+    np.save(os.path.join(path, "counters.npy"), np.asarray(counters, dtype=np.float64))
+
+
 def group_bench(args):
     """--mode group: one process, one group context over --gpus devices (include/frm.h ABI 5). The
     timed region is --steps frm_render calls (frames_in_flight slots rotate; each frame's bands are
@@ -412,6 +455,7 @@ def group_bench(args):
             r.render(stats=False)
         r.synchronize()
         elapsed = time.perf_counter() - t0
+        last = r.read_frame() if args.dump_outputs else None  # the last timed frame
         steps_total = 0
         counters = [0] * len(COUNTER_NAMES)
         for k, p in enumerate(frames):
@@ -420,14 +464,15 @@ def group_bench(args):
             steps_total += st["march_steps"]
             counters = [a + st[n] for a, n in zip(counters, COUNTER_NAMES)]
             if k == 0:
-                import numpy as np
-                sha = hashlib.sha256(np.ascontiguousarray(r.read_frame()).tobytes()).hexdigest()
+                if args.full:
+                    import numpy as np
+                    sha = hashlib.sha256(np.ascontiguousarray(r.read_frame()).tobytes()).hexdigest()
                 if w.moving:
                     break
         if w.moving:  # the stats pass rendered frame 0 only
             steps_total = None
-    key = golden_key(args.workload, args.pose)
-    gold = json.load(open(GOLDEN)).get(key) if os.path.exists(GOLDEN) else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, counters)
     out = {
         "metric": METRIC,
         "value": None if steps_total is None else steps_total / elapsed / 1e9,
@@ -450,14 +495,17 @@ def group_bench(args):
                                   + " to device 0, reassembled there (one process)"},
         "launcher": "single process (--mode group, frm_config.device_count)",
         "frames_per_sec": args.steps / elapsed,
-        "frame_sha256": sha,
-        "frame_sha_ok": None if gold is None else sha == gold["sha256"],
-        "frame_golden": None if gold is None else f"tests/golden/fullsize.json[{key}]",
     }
-    if not w.moving:
-        cc = counters_check(counters, args.workload, args.pose, args.steps)
-        if cc is not None:
-            out.update(cc)
+    if args.full:  # frame 0 and the summed counters against the oracle's goldens
+        key = golden_key(args.workload, args.pose)
+        gold = json.load(open(GOLDEN)).get(key) if os.path.exists(GOLDEN) else None
+        out.update({"frame_sha256": sha,
+                    "frame_sha_ok": None if gold is None else sha == gold["sha256"],
+                    "frame_golden": None if gold is None else f"tests/golden/fullsize.json[{key}]"})
+        if not w.moving:
+            cc = counters_check(counters, args.workload, args.pose, args.steps)
+            if cc is not None:
+                out.update(cc)
     print(json.dumps(out))
 
 
@@ -629,7 +677,8 @@ def main():
     begin.record(main_stream)
     for s in streams:
         s.wait_event(begin)
-    # rank 0 keeps timed frame 0 (for the golden-frame check) with one device copy on its stream
+    # rank 0 keeps timed frame 0 (for --full's golden-frame check) with one device copy on its
+    # stream; a plain run keeps it too, so both time the same region
     first = torch.empty(w.width * w.height * 4, dtype=torch.uint8, device=dev) if rank == 0 else None
     t0 = time.perf_counter()
     tf.run(args.steps, before_frame, capture=first)
@@ -645,10 +694,12 @@ def main():
     elapsed = t1 - t0
     span_ms = begin.elapsed_time(end)
     launch_ms = sum(a.elapsed_time(b) for a, b in kev) / max(1, len(kev))
+    # --dump-outputs: the last timed frame (rank 0: gathered and reassembled), still in its buffer
+    last = tf.output().cpu().numpy() if args.dump_outputs and rank == 0 else None
 
-    # the drop-in binding's one-frame-per-frm_render loop on the same workload (rank 0, N = 1)
+    # --full: the drop-in binding's one-frame-per-frm_render loop on the same workload (rank 0, N = 1)
     dropin = None
-    if world == 1 and not args.no_dropin:
+    if args.full and world == 1 and not args.no_dropin:
         dropin = dropin_loop(frm, torch, w, args, flags, local, camera)
         if int(os.environ["GPU_MAX_HW_QUEUES"]) != 4:
             q4 = dropin_q4(args)
@@ -678,7 +729,9 @@ def main():
         # rank's frame) and the device time per frame
         wom_per_frame = st["wom_ops"] / args.steps / (world if split == 1 else 1)
         achieved = st["wom_ops"] / args.steps / world / frame_s / 1e12  # per GPU
-        pmc = pmc_summary(args.workload, world, args.math) or {}
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last, c)
+        pmc = (pmc_summary(args.workload, world, args.math) if args.full else None) or {}
         out = {
             "metric": METRIC,
             "value": steps_total / elapsed / 1e9,
@@ -742,15 +795,15 @@ def main():
             out["comm"] = {"backend": backend, "ranks": comm_ranks,
                            "data_path": "dist.gather of row bands to rank 0" if split > 1 else "none (timing only)"}
             out["rccl_ranks"] = comm_ranks if backend == "nccl" else None
-        if args.math == "exact":
+        if args.full and args.math == "exact":
             out.update(frame_check(first, args.workload, args.pose))
-        else:  # no golden: the hardware-math frame differs from the oracle's by design
+        elif args.full:  # no golden: the hardware-math frame differs from the oracle's by design
             out.update({"frame_sha256": hashlib.sha256(first.cpu().numpy().tobytes()).hexdigest(),
                         "frame_sha_ok": None, "frame_golden": "none (FRM_FLAG_HW_MATH is not bit-exact)"})
         # every timed frame is frame 0 (fixed workloads; a row split's ranks sum to whole frames):
         # the summed counters must be steps x the golden frame's, or the roofline is not reported
         cc = None
-        if args.math == "exact" and not w.moving and not afr:
+        if args.full and args.math == "exact" and not w.moving and not afr:
             cc = counters_check(c, args.workload, args.pose, args.steps)
         if cc is not None:
             out.update(cc)
@@ -759,7 +812,7 @@ def main():
                     out["roofline"][k] = None
         if dropin:
             out.update(dropin)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(params, w, args.cpu_seconds)
         print(json.dumps(out))
         if cc is not None and not cc["counters_ok"]:

@@ -20,7 +20,7 @@ def test_bench_launches_its_own_ranks(split):
     env = dict(os.environ, FRM_BENCH_SHARED_DEVICE="1", FRM_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "C2", "--split", split,
-           "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+           "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"]
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=110, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -8,7 +8,7 @@ ARGS=${ARGS:---steps 30 --warmup 3}
 mkdir -p "$OUT"
 for round in $(seq 1 ${ROUNDS:-3}); do
   for n in $VARIANTS; do
-    FRM_LIB=$PWD/fractal-ray-marching_amd/ab/$n.so timeout -k 10 300 python bench.py $ARGS --no-cpu-baseline --no-dropin \
+    FRM_LIB=$PWD/fractal-ray-marching_amd/ab/$n.so timeout -k 10 300 python bench.py $ARGS --full --no-cpu-baseline --no-dropin \
       > "$OUT/${n}_$round.json" 2> "$OUT/${n}_$round.err"
     rc=$?
     if [ $rc -ne 0 ] && [ $rc -ne 3 ]; then echo "bench $n rc=$rc"; tail -5 "$OUT/${n}_$round.err"; exit $rc; fi

@@ -18,7 +18,7 @@ tests)
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || { tail "$OUT/smoke.log"; exit 1; }
   tail -1 "$OUT/smoke.log"
   # the driver's command (defaults: 30 timed frames, one launch of 30 on one GPU)
-  timeout -k 10 400 python bench.py > "$OUT/bench_HEADLINE.json" 2> "$OUT/bench.err" || { tail "$OUT/bench.err"; exit 1; }
+  timeout -k 10 400 python bench.py --full > "$OUT/bench_HEADLINE.json" 2> "$OUT/bench.err" || { tail "$OUT/bench.err"; exit 1; }
   timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python3 bench.py --no-cpu-baseline --no-dropin > "$OUT/prof_bench.json" 2> "$OUT/prof.err" || { tail "$OUT/prof.err"; exit 1; }
   B=$(python3 -c "import json;print(json.load(open('$OUT/prof_bench.json'))['config']['frames_per_launch'])")
   python tools/rocprof_timed.py "$(find "$OUT/prof" -name '*kernel_trace.csv' | head -1)" 1 "$B" > "$OUT/rocprof_timed_HEADLINE.txt"
@@ -27,7 +27,7 @@ tests)
 configs)
   for spec in "HEADLINE:" "HEADLINE_FLY:" "C1:" "C2:" "C3:" "C4:" "C5:--steps 3 --warmup 1" "HEADLINE:--math hw"; do
     wl=${spec%%:*}; a=${spec#*:}; tag=$wl; [ "$a" = "--math hw" ] && tag=${wl}_hw_math
-    timeout -k 10 400 python bench.py --workload $wl $a --no-cpu-baseline > "$OUT/$tag.json" 2> "$OUT/$tag.err" || { echo "bench $tag failed"; tail -5 "$OUT/$tag.err"; exit 1; }
+    timeout -k 10 400 python bench.py --workload $wl $a --full --no-cpu-baseline > "$OUT/$tag.json" 2> "$OUT/$tag.err" || { echo "bench $tag failed"; tail -5 "$OUT/$tag.err"; exit 1; }
     python -c "import json;d=json.load(open('$OUT/$tag.json'));r=d['roofline'];print('$tag', round(d['value'],3), 'G/s', round(d['ms_per_step'],3), 'ms', 'dropin', round(d.get('dropin_ms_per_frame') or 0,3), 'frac', round(r['frac'],4), 'sha_ok', d.get('frame_sha_ok'))"
   done
   echo CONFIGS_OK ;;
