@@ -229,9 +229,142 @@ typedef struct {
   vec3 origin;
 } om_frame;
 
+/* ---- domain census (tests/test_edge_census.py): which numerically delicate operand ranges the
+ * values computed here fall into. It describes the inputs of the operations, never the
+ * product's choices; the thresholds are the operand-domain bounds the product documents for its
+ * device fast paths (DESIGN.md sections 2 and 5), named once: */
+static const float CEN_COMPONENT_MIN = 0x1p-60f; /* tame body: every |component| of z is 0 or >= this */
+static const float CEN_R_MIN = 0x1p-13f;         /* tame body: r = length(z) >= this */
+static const float CEN_DOT_LO = 0x1p-96f;        /* rsq-based length: dot(z, z) within [LO, HI] */
+static const float CEN_DOT_HI = 0x1p126f;
+static const float CEN_T_TINY = 0x1p-60f;        /* div_tame: |operand| within [2^-60, 2^40] */
+static const float CEN_DR_BIG = 0x1p64f;         /* far above div_tame's divisors (2^40); 1 / dr^2 underflows */
+static const float CEN_DR_HUGE = 0x1p125f;       /* rcp_rn: RN(1 / b) for |b| within [2^-125, 2^125] */
+static const float CEN_NORMAL_MIN = 0x1p-126f;   /* smallest positive normal f32 */
+
+enum { /* counters (u64); order = frm_oracle.py CENSUS_COUNTS */
+  CN_MB_BODIES, CN_MB_COMP_ZERO, CN_MB_COMP_TINY, CN_MB_R_SMALL,
+  CN_MB_LENGTHS, CN_MB_DOT_WIDE,
+  CN_MB_DISTS, CN_MB_MAG_NOT_NORMAL, CN_MB_DR_GE_2P64, CN_MB_DR_GE_2P125, CN_MB_DR_INF, CN_MB_DR_NAN,
+  CN_MB_DE_NAN, CN_MB_DE_NEG, CN_MB_DE_ZERO, CN_MB_DE_SUBNORMAL,
+  /* closeness divisions d / t: primary march, then the same eight for the shadow march */
+  CN_P_DIVS, CN_P_T0_DPOS, CN_P_T0_DNONPOS, CN_P_T0_DNAN, CN_P_T_TINY, CN_P_Q_SUBNORMAL, CN_P_Q_INF, CN_P_Q_NAN,
+  CN_S_DIVS, CN_S_T0_DPOS, CN_S_T0_DNONPOS, CN_S_T0_DNAN, CN_S_T_TINY, CN_S_Q_SUBNORMAL, CN_S_Q_INF, CN_S_Q_NAN,
+  /* march ends: primary, then shadow */
+  CN_P_END_HIT, CN_P_END_STEPS, CN_P_END_FAR, CN_P_END_NAN,
+  CN_S_END_HIT, CN_S_END_STEPS, CN_S_END_FAR, CN_S_END_NAN,
+  /* distance estimates of the other families */
+  CN_DE_EVALS, CN_DE_NAN, CN_DE_INF, CN_DE_ZERO, CN_DE_SUBNORMAL,
+  CN_COUNT
+};
+enum { /* extremes (f32); order = frm_oracle.py CENSUS_EXTREMES. A max starts at 0, a min at +inf */
+  CX_MB_DR_MAX_FINITE, CX_P_T_MAX_FINITE, CX_S_T_MAX_FINITE, CX_MAX_COUNT,
+  CX_MB_DE_MIN_NONZERO = CX_MAX_COUNT, CX_P_T_MIN_NONZERO, CX_S_T_MIN_NONZERO,
+  CX_COUNT
+};
+typedef struct {
+  uint64_t n[CN_COUNT];
+  float x[CX_COUNT];
+} om_census;
+
+static void census_init(om_census* K) {
+  memset(K, 0, sizeof(*K));
+  for (int i = CX_MAX_COUNT; i < CX_COUNT; ++i) K->x[i] = INFINITY;
+}
+static void census_merge(om_census* into, const om_census* K) {
+  for (int i = 0; i < CN_COUNT; ++i) into->n[i] += K->n[i];
+  for (int i = 0; i < CX_MAX_COUNT; ++i) into->x[i] = fmaxf(into->x[i], K->x[i]);
+  for (int i = CX_MAX_COUNT; i < CX_COUNT; ++i) into->x[i] = fminf(into->x[i], K->x[i]);
+}
+static int is_subnormal(float v) { return v != 0.0f && fabsf(v) < CEN_NORMAL_MIN; }
+static int is_finite(float v) { return fabsf(v) < INFINITY; }
+
 typedef struct {
   uint64_t primary, shadow, normal, hits, pixels, bodies, bailouts;
+  om_census* census; /* NULL unless a census was asked for; per thread like the counters */
 } om_counts;
+
+static void census_mb_length(om_counts* C, float dot) {
+  om_census* K = C->census;
+  if (!K) return;
+  K->n[CN_MB_LENGTHS]++;
+  if (!(dot >= CEN_DOT_LO && dot <= CEN_DOT_HI)) K->n[CN_MB_DOT_WIDE]++;
+}
+static void census_mb_body(om_counts* C, vec3 z, float r) {
+  om_census* K = C->census;
+  if (!K) return;
+  const float m = fminf(fminf(fabsf(z.x), fabsf(z.y)), fabsf(z.z));
+  K->n[CN_MB_BODIES]++;
+  if (m == 0.0f) K->n[CN_MB_COMP_ZERO]++;
+  else if (m < CEN_COMPONENT_MIN) K->n[CN_MB_COMP_TINY]++;
+  if (r < CEN_R_MIN) K->n[CN_MB_R_SMALL]++;
+}
+static void census_mb_distance(om_counts* C, float magnitude, float dr, float de) {
+  om_census* K = C->census;
+  if (!K) return;
+  const float a = fabsf(dr), e = fabsf(de);
+  K->n[CN_MB_DISTS]++;
+  if (!(magnitude >= CEN_NORMAL_MIN && magnitude < INFINITY)) K->n[CN_MB_MAG_NOT_NORMAL]++;
+  if (dr != dr) K->n[CN_MB_DR_NAN]++;
+  else if (a == INFINITY) K->n[CN_MB_DR_INF]++;
+  else {
+    if (a >= CEN_DR_BIG) K->n[CN_MB_DR_GE_2P64]++;
+    if (a >= CEN_DR_HUGE) K->n[CN_MB_DR_GE_2P125]++;
+    K->x[CX_MB_DR_MAX_FINITE] = fmaxf(K->x[CX_MB_DR_MAX_FINITE], a);
+  }
+  if (de != de) K->n[CN_MB_DE_NAN]++;
+  else if (de == 0.0f) K->n[CN_MB_DE_ZERO]++;
+  else {
+    if (de < 0.0f) K->n[CN_MB_DE_NEG]++;
+    if (is_subnormal(de)) K->n[CN_MB_DE_SUBNORMAL]++;
+    K->x[CX_MB_DE_MIN_NONZERO] = fminf(K->x[CX_MB_DE_MIN_NONZERO], e);
+  }
+}
+static void census_de(om_counts* C, float de) {
+  om_census* K = C->census;
+  if (!K) return;
+  K->n[CN_DE_EVALS]++;
+  if (de != de) K->n[CN_DE_NAN]++;
+  else if (!is_finite(de)) K->n[CN_DE_INF]++;
+  else if (de == 0.0f) K->n[CN_DE_ZERO]++;
+  else if (is_subnormal(de)) K->n[CN_DE_SUBNORMAL]++;
+}
+/* one closeness division d / t of a march; shadow selects the second group */
+static void census_closeness(om_counts* C, int shadow, float d, float t, float q) {
+  om_census* K = C->census;
+  if (!K) return;
+  uint64_t* n = K->n + (shadow ? CN_S_DIVS : CN_P_DIVS);
+  const float a = fabsf(t);
+  n[0]++;
+  if (t == 0.0f) {
+    if (d != d) n[3]++;
+    else if (d > 0.0f) n[1]++;
+    else n[2]++;
+  } else if (a < CEN_T_TINY) {
+    n[4]++;
+  }
+  if (is_subnormal(q)) n[5]++;
+  if (q == INFINITY || q == -INFINITY) n[6]++;
+  if (q != q) n[7]++;
+  if (t != 0.0f && t == t) {
+    float* mn = &K->x[shadow ? CX_S_T_MIN_NONZERO : CX_P_T_MIN_NONZERO];
+    *mn = fminf(*mn, a);
+  }
+  if (is_finite(t)) {
+    float* mx = &K->x[shadow ? CX_S_T_MAX_FINITE : CX_P_T_MAX_FINITE];
+    *mx = fmaxf(*mx, a);
+  }
+}
+static void census_march_end(om_counts* C, int shadow, int hit, uint32_t it, uint32_t max_steps, float total,
+                             float max_total) {
+  om_census* K = C->census;
+  if (!K) return;
+  uint64_t* n = K->n + (shadow ? CN_S_END_HIT : CN_P_END_HIT);
+  if (hit) n[0]++;
+  else if (total != total) n[3]++;
+  else if (total >= max_total) n[2]++;
+  else if (it >= max_steps) n[1]++;
+}
 
 /* animate_between, fragment.wgsl:80-82 (0.5 + 0.5*s and a + (b-a)*w contracted) */
 static float animate_between(const om_frame* F, float a, float b) {
@@ -382,10 +515,12 @@ static float mandelbulb(const om_frame* F, vec3 position, om_counts* C) {
   float magnitude_derivative = 1.0f, magnitude = 0.0f;
   for (uint32_t i = 0; i <= F->num_iterations; i++) {
     magnitude = vlength(current);
+    census_mb_length(C, vdot(current, current));
     if (magnitude > bailout) {
       C->bailouts++;
       break;
     }
+    census_mb_body(C, current, magnitude);
     float theta = b_acos(m, current.z / magnitude);
     float phi = b_atan2(m, current.y, current.x);
     /* fragment.wgsl:254, 257; frm v3: pow(magnitude, power) evaluated as
@@ -399,18 +534,21 @@ static float mandelbulb(const om_frame* F, vec3 position, om_counts* C) {
     current = vmadd(exp_magnitude, V(st * cp, sp * st, ct), position);
     C->bodies++;
   }
-  return ((0.5f * b_log(m, magnitude)) * magnitude) / magnitude_derivative;
+  const float de = ((0.5f * b_log(m, magnitude)) * magnitude) / magnitude_derivative;
+  census_mb_distance(C, magnitude, magnitude_derivative, de);
+  return de;
 }
 
 static float scene(const om_frame* F, vec3 p, vec3* color, om_counts* C) {
   float d;
   switch (F->family) {
-    case 1: d = sierpinski(F, p); if (color) *color = colorize(vscale(p, 1.5f)); return d;
+    case 1: d = sierpinski(F, p); census_de(C, d); if (color) *color = colorize(vscale(p, 1.5f)); return d;
     case 2: d = koch(F, p); break;
     case 3: d = mandelbulb(F, p, C); break;
     case 4: d = vlength(p) - 0.5f; break;
     default: d = menger_sponge(F, p); break;
   }
+  if (F->family != 3) census_de(C, d);
   if (color) *color = colorize(p);
   return d;
 }
@@ -426,7 +564,7 @@ typedef struct {
   uint32_t steps;
 } march_result;
 
-static march_result march(const om_frame* F, vec3 start, vec3 dir, uint64_t* evals, om_counts* C) {
+static march_result march(const om_frame* F, vec3 start, vec3 dir, uint64_t* evals, om_counts* C, int shadow) {
   march_result r;
   r.position = start;
   r.distance = -INF_1E20;
@@ -439,6 +577,7 @@ static march_result march(const om_frame* F, vec3 start, vec3 dir, uint64_t* eva
     float d = scene(F, p, &col, C);
     (*evals)++;
     closeness = wmin(closeness, d / total);
+    census_closeness(C, shadow, d, total, d / total);
     if (d <= MIN_DISTANCE) {
       r.color = col;
       r.distance = total;
@@ -447,6 +586,7 @@ static march_result march(const om_frame* F, vec3 start, vec3 dir, uint64_t* eva
     }
     total += d;
   }
+  census_march_end(C, shadow, r.distance >= 0.0f, it, F->max_steps, total, MAX_TOTAL_DISTANCE);
   r.closeness = closeness;
   r.steps = it;
   return r;
@@ -512,7 +652,7 @@ static vec3 shade_hit(const om_frame* F, vec3 camera_direction, vec3 color, uint
  * trace) the OM_TRACE_FLOATS geometric shading inputs */
 static vec3 fragment(const om_frame* F, uint32_t x, uint32_t y, om_counts* C, uint32_t* info, float* trace) {
   vec3 camera_direction = camera_dir(F, x, y);
-  march_result obj = march(F, F->origin, camera_direction, &C->primary, C);
+  march_result obj = march(F, F->origin, camera_direction, &C->primary, C, 0);
   vec3 color = obj.color;
   uint32_t inf = obj.steps << 8;
   if (trace) {
@@ -526,7 +666,7 @@ static vec3 fragment(const om_frame* F, uint32_t x, uint32_t y, om_counts* C, ui
     if (n.x != n.x) inf |= INFO_ZERO_NORMAL;
     vec3 start = V(fmaf(n.x * 2.0f, MIN_DISTANCE, obj.position.x), fmaf(n.y * 2.0f, MIN_DISTANCE, obj.position.y),
                    fmaf(n.z * 2.0f, MIN_DISTANCE, obj.position.z));
-    march_result sun = march(F, start, TO_SUN, &C->shadow, C);
+    march_result sun = march(F, start, TO_SUN, &C->shadow, C, 1);
     if (sun.distance >= 0.0f) inf |= INFO_SUN_HIT;
     if (sun.closeness != sun.closeness || sun.closeness == -INFINITY) inf |= INFO_SHADOW_FIRST_NONPOS;
     if (trace) {
@@ -579,12 +719,16 @@ typedef struct {
   uint32_t next; /* atomic row cursor (rayon-like dynamic schedule) */
   pthread_mutex_t mu;
   om_counts total;
+  om_census* census; /* summed over the threads under mu (sums, max and min: any order) */
 } job;
 
 static void* worker(void* arg) {
   job* J = (job*)arg;
   om_counts C;
+  om_census K;
   memset(&C, 0, sizeof(C));
+  census_init(&K);
+  if (J->census) C.census = &K;
   const uint32_t W = J->F->width;
   for (;;) {
     uint32_t r = __atomic_fetch_add(&J->next, 1u, __ATOMIC_RELAXED);
@@ -616,6 +760,7 @@ static void* worker(void* arg) {
   J->total.pixels += C.pixels;
   J->total.bodies += C.bodies;
   J->total.bailouts += C.bailouts;
+  if (J->census) census_merge(J->census, &K);
   pthread_mutex_unlock(&J->mu);
   return NULL;
 }
@@ -639,10 +784,10 @@ static void frame_from_params(om_frame* F, const uint8_t* params96, uint32_t wid
 /* Render `nrows` rows (rows[i], or 0..nrows-1 when rows == NULL) of a width x height frame.
  * counters (8 x u64, same order as libfrm's device counters): pixels, hits, primary
  * steps, shadow steps, normal evals, Mandelbulb bodies, bailouts, 0. */
-int om_render_trace(const uint8_t* params96, uint32_t width, uint32_t height, uint32_t max_steps,
-                    uint32_t flags, int mode, const uint32_t* rows, uint32_t nrows, int threads,
-                    uint8_t* out_rgba, uint64_t* counters, float* out_linear, uint32_t* out_info,
-                    float* out_trace) {
+static int render_impl(const uint8_t* params96, uint32_t width, uint32_t height, uint32_t max_steps,
+                       uint32_t flags, int mode, const uint32_t* rows, uint32_t nrows, int threads,
+                       uint8_t* out_rgba, uint64_t* counters, float* out_linear, uint32_t* out_info,
+                       float* out_trace, om_census* census) {
   if (!params96 || !out_rgba || width == 0 || height == 0 || threads < 1) return 1;
   for (uint32_t i = 0; rows && i < nrows; ++i)
     if (rows[i] >= height) return 1;
@@ -658,6 +803,7 @@ int om_render_trace(const uint8_t* params96, uint32_t width, uint32_t height, ui
   J.linear = out_linear;
   J.info = out_info;
   J.trace = out_trace;
+  J.census = census;
   pthread_mutex_init(&J.mu, NULL);
   pthread_t* tid = (pthread_t*)calloc((size_t)threads, sizeof(pthread_t));
   if (!tid) return 2;
@@ -680,6 +826,41 @@ int om_render_trace(const uint8_t* params96, uint32_t width, uint32_t height, ui
     counters[7] = 0;
   }
   return 0;
+}
+
+int om_render_trace(const uint8_t* params96, uint32_t width, uint32_t height, uint32_t max_steps,
+                    uint32_t flags, int mode, const uint32_t* rows, uint32_t nrows, int threads,
+                    uint8_t* out_rgba, uint64_t* counters, float* out_linear, uint32_t* out_info,
+                    float* out_trace) {
+  return render_impl(params96, width, height, max_steps, flags, mode, rows, nrows, threads, out_rgba, counters,
+                     out_linear, out_info, out_trace, NULL);
+}
+
+/* The census layout, so that a binding can check its name tables against it. */
+void om_census_layout(uint32_t* counts, uint32_t* extremes, uint32_t* maxima) {
+  *counts = CN_COUNT;
+  *extremes = CX_COUNT;
+  *maxima = CX_MAX_COUNT;
+}
+static void census_out(const om_census* K, uint64_t* out_n, float* out_x) {
+  memcpy(out_n, K->n, sizeof(K->n));
+  memcpy(out_x, K->x, sizeof(K->x));
+}
+
+/* om_render_trace plus the domain census of the rendered rows: out_census_n[CN_COUNT] and
+ * out_census_x[CX_COUNT] (an extreme that was never met stays 0 for a maximum, +inf for a
+ * minimum). Every other output is om_render_trace's, byte for byte. */
+int om_render_census(const uint8_t* params96, uint32_t width, uint32_t height, uint32_t max_steps,
+                     uint32_t flags, int mode, const uint32_t* rows, uint32_t nrows, int threads,
+                     uint8_t* out_rgba, uint64_t* counters, float* out_linear, uint32_t* out_info,
+                     float* out_trace, uint64_t* out_census_n, float* out_census_x) {
+  if (!out_census_n || !out_census_x) return 1;
+  om_census K;
+  census_init(&K);
+  int rc = render_impl(params96, width, height, max_steps, flags, mode, rows, nrows, threads, out_rgba, counters,
+                       out_linear, out_info, out_trace, &K);
+  if (rc == 0) census_out(&K, out_census_n, out_census_x);
+  return rc;
 }
 
 int om_render(const uint8_t* params96, uint32_t width, uint32_t height, uint32_t max_steps, uint32_t flags,
@@ -715,12 +896,13 @@ int om_shade_trace(const uint8_t* params96, uint32_t width, uint32_t height, uin
 }
 
 /* scene() at n points (xyz interleaved): distance, colour, Mandelbulb counts. */
-int om_scene_de(const uint8_t* params96, uint32_t flags, int mode, const float* pts, uint32_t n, float* out_d,
-                float* out_color, uint64_t* out_counts) {
+static int scene_de_impl(const uint8_t* params96, uint32_t flags, int mode, const float* pts, uint32_t n,
+                         float* out_d, float* out_color, uint64_t* out_counts, om_census* census) {
   om_frame F;
   frame_from_params(&F, params96, 1, 1, 0, flags, mode);
   om_counts C;
   memset(&C, 0, sizeof(C));
+  C.census = census;
   for (uint32_t i = 0; i < n; ++i) {
     vec3 col;
     out_d[i] = scene(&F, V(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]), &col, &C);
@@ -735,6 +917,22 @@ int om_scene_de(const uint8_t* params96, uint32_t flags, int mode, const float* 
     out_counts[1] = C.bailouts;
   }
   return 0;
+}
+
+int om_scene_de(const uint8_t* params96, uint32_t flags, int mode, const float* pts, uint32_t n, float* out_d,
+                float* out_color, uint64_t* out_counts) {
+  return scene_de_impl(params96, flags, mode, pts, n, out_d, out_color, out_counts, NULL);
+}
+/* om_scene_de plus the domain census of the n evaluations (layout as om_render_census). */
+int om_scene_de_census(const uint8_t* params96, uint32_t flags, int mode, const float* pts, uint32_t n,
+                       float* out_d, float* out_color, uint64_t* out_counts, uint64_t* out_census_n,
+                       float* out_census_x) {
+  if (!out_census_n || !out_census_x) return 1;
+  om_census K;
+  census_init(&K);
+  int rc = scene_de_impl(params96, flags, mode, pts, n, out_d, out_color, out_counts, &K);
+  if (rc == 0) census_out(&K, out_census_n, out_census_x);
+  return rc;
 }
 
 /* Builtins on arrays: fn 0 sin, 1 cos, 2 acos, 3 atan2(a,b), 4 log, 5 log2, 6 exp2,

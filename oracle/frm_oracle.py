@@ -27,6 +27,20 @@ TRACE_FIELDS = ("hit", "steps", "nx", "ny", "nz", "sun_hit", "sun_closeness", "c
 MATH_FN = {"sin": 0, "cos": 1, "acos": 2, "atan2": 3, "log": 4, "log2": 5, "exp2": 6,
            "pow": 7, "sqrt": 8, "div": 9}
 
+# domain census (render(census=True), scene_de_census): names in frm_oracle.c's enum order
+_CLOSENESS = ("divs", "t0_dpos", "t0_dnonpos", "t0_dnan", "t_tiny", "q_subnormal", "q_inf", "q_nan")
+_ENDS = ("end_hit", "end_steps", "end_far", "end_nan")
+CENSUS_COUNTS = (("mb_bodies", "mb_comp_zero", "mb_comp_tiny", "mb_r_small", "mb_lengths", "mb_dot_wide",
+                  "mb_dists", "mb_mag_not_normal", "mb_dr_ge_2p64", "mb_dr_ge_2p125", "mb_dr_inf", "mb_dr_nan",
+                  "mb_de_nan", "mb_de_neg", "mb_de_zero", "mb_de_subnormal")
+                 + tuple("primary_" + n for n in _CLOSENESS) + tuple("shadow_" + n for n in _CLOSENESS)
+                 + tuple("primary_" + n for n in _ENDS) + tuple("shadow_" + n for n in _ENDS)
+                 + ("de_evals", "de_nan", "de_inf", "de_zero", "de_subnormal"))
+# a maximum that was never met is 0, a minimum +inf
+CENSUS_EXTREMES = ("mb_dr_max_finite", "primary_t_max_finite", "shadow_t_max_finite",
+                   "mb_de_min_nonzero", "primary_t_min_nonzero", "shadow_t_min_nonzero")
+CENSUS_MAXIMA = 3
+
 _lib = None
 
 
@@ -53,6 +67,13 @@ def load():
         lib.om_scene_de.argtypes = [u8p, ctypes.c_uint32, ctypes.c_int, f32p, ctypes.c_uint32, f32p,
                                     f32p, u64p]
         lib.om_scene_de.restype = ctypes.c_int
+        lib.om_render_census.argtypes = lib.om_render_trace.argtypes + [u64p, f32p]
+        lib.om_render_census.restype = ctypes.c_int
+        lib.om_scene_de_census.argtypes = lib.om_scene_de.argtypes + [u64p, f32p]
+        lib.om_scene_de_census.restype = ctypes.c_int
+        lay = (ctypes.c_uint32 * 3)()
+        lib.om_census_layout(ctypes.byref(lay, 0), ctypes.byref(lay, 4), ctypes.byref(lay, 8))
+        assert tuple(lay) == (len(CENSUS_COUNTS), len(CENSUS_EXTREMES), CENSUS_MAXIMA), tuple(lay)
         lib.om_math.argtypes = [ctypes.c_int, ctypes.c_int, f32p, f32p, ctypes.c_uint32, f32p]
         lib.om_math.restype = ctypes.c_int
         lib.om_srgb_thresholds.argtypes = [f32p]
@@ -77,9 +98,10 @@ def _params_buf(params):
 
 
 def render(params, width, height, max_steps, flags=0, mode=MODE_FRM, rows=None, threads=None,
-           linear=False, info=False, trace=False):
+           linear=False, info=False, trace=False, census=False):
     """Render rows (default all) -> dict(rgba=[n,W,4] u8, counters=[8] u64, ...); info: the
-    per-pixel INFO_* bits | primary steps << 8; trace: [n,W,len(TRACE_FIELDS)] f32."""
+    per-pixel INFO_* bits | primary steps << 8; trace: [n,W,len(TRACE_FIELDS)] f32; census: the
+    domain census of the rendered rows, a dict over CENSUS_COUNTS (int) and CENSUS_EXTREMES (float)."""
     lib = load()
     pb = _params_buf(params)
     if rows is None:
@@ -93,10 +115,15 @@ def render(params, width, height, max_steps, flags=0, mode=MODE_FRM, rows=None, 
     lin = np.zeros((nrows, width, 3), dtype=np.float32) if linear else None
     inf = np.zeros((nrows, width), dtype=np.uint32) if info else None
     tr = np.zeros((nrows, width, len(TRACE_FIELDS)), dtype=np.float32) if trace else None
-    rc = lib.om_render_trace(pb.ctypes.data, width, height, max_steps, flags, mode, rows_ptr, nrows, threads,
-                             rgba.ctypes.data, counters.ctypes.data,
-                             lin.ctypes.data if linear else None, inf.ctypes.data if info else None,
-                             tr.ctypes.data if trace else None)
+    args = (pb.ctypes.data, width, height, max_steps, flags, mode, rows_ptr, nrows, threads,
+            rgba.ctypes.data, counters.ctypes.data,
+            lin.ctypes.data if linear else None, inf.ctypes.data if info else None,
+            tr.ctypes.data if trace else None)
+    if census:
+        cn, cx = _census_arrays()
+        rc = lib.om_render_census(*args, cn.ctypes.data, cx.ctypes.data)
+    else:
+        rc = lib.om_render_trace(*args)
     if rc != 0:
         raise RuntimeError(f"om_render failed ({rc})")
     out = {"rgba": rgba, "counters": counters}
@@ -106,6 +133,26 @@ def render(params, width, height, max_steps, flags=0, mode=MODE_FRM, rows=None, 
         out["info"] = inf
     if trace:
         out["trace"] = tr
+    if census:
+        out["census"] = _census_dict(cn, cx)
+    return out
+
+
+def _census_arrays():
+    return np.zeros(len(CENSUS_COUNTS), dtype=np.uint64), np.zeros(len(CENSUS_EXTREMES), dtype=np.float32)
+
+
+def _census_dict(cn, cx):
+    d = {k: int(v) for k, v in zip(CENSUS_COUNTS, cn)}
+    d.update({k: float(v) for k, v in zip(CENSUS_EXTREMES, cx)})
+    return d
+
+
+def merge_census(a, b):
+    """The census of two runs together (counts add; extremes take the max / min)."""
+    out = {k: a[k] + b[k] for k in CENSUS_COUNTS}
+    out.update({k: max(a[k], b[k]) for k in CENSUS_EXTREMES[:CENSUS_MAXIMA]})
+    out.update({k: min(a[k], b[k]) for k in CENSUS_EXTREMES[CENSUS_MAXIMA:]})
     return out
 
 
@@ -133,6 +180,22 @@ def scene_de(params, points, flags=0, mode=MODE_FRM):
     lib.om_scene_de(_params_buf(params).ctypes.data, flags, mode, pts.ctypes.data, n, d.ctypes.data,
                     col.ctypes.data, cnt.ctypes.data)
     return d, col, cnt
+
+
+def scene_de_census(params, points, flags=0, mode=MODE_FRM):
+    """scene_de plus the domain census of the evaluations: (d, col, cnt, census)."""
+    lib = load()
+    pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    n = pts.shape[0]
+    d = np.zeros(n, dtype=np.float32)
+    col = np.zeros((n, 3), dtype=np.float32)
+    cnt = np.zeros(2, dtype=np.uint64)
+    cn, cx = _census_arrays()
+    rc = lib.om_scene_de_census(_params_buf(params).ctypes.data, flags, mode, pts.ctypes.data, n, d.ctypes.data,
+                                col.ctypes.data, cnt.ctypes.data, cn.ctypes.data, cx.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"om_scene_de_census failed ({rc})")
+    return d, col, cnt, _census_dict(cn, cx)
 
 
 def math_fn(name, a, b=None, mode=MODE_FRM):

@@ -19,6 +19,13 @@ int om_render(const uint8_t* params96, uint32_t width, uint32_t height, uint32_t
               uint64_t* counters, float* out_linear, uint32_t* out_info);
 int om_scene_de(const uint8_t* params96, uint32_t flags, int mode, const float* pts, uint32_t n, float* out_d,
                 float* out_color, uint64_t* out_counts);
+int om_render_census(const uint8_t* params96, uint32_t width, uint32_t height, uint32_t max_steps, uint32_t flags,
+                     int mode, const uint32_t* rows, uint32_t nrows, int threads, uint8_t* out_rgba,
+                     uint64_t* counters, float* out_linear, uint32_t* out_info, float* out_trace,
+                     uint64_t* out_census_n, float* out_census_x);
+int om_scene_de_census(const uint8_t* params96, uint32_t flags, int mode, const float* pts, uint32_t n, float* out_d,
+                       float* out_color, uint64_t* out_counts, uint64_t* out_census_n, float* out_census_x);
+void om_census_layout(uint32_t* counts, uint32_t* extremes, uint32_t* maxima);
 int om_math(int fn, int mode, const float* a, const float* b, uint32_t n, float* out);
 int om_blit(const uint8_t* src, uint32_t sw, uint32_t sh, uint8_t* dst, uint32_t dw, uint32_t dh, uint32_t flags);
 }
@@ -59,6 +66,10 @@ int main(int argc, char** argv) {
   // oracle: every scene, iteration counts including the i32 shift wrap, sphere flag, both
   // math modes, a row subset, ragged sizes
   const uint32_t sizes[][2] = {{1, 1}, {33, 17}, {48, 27}};
+  uint32_t cen_counts = 0, cen_extremes = 0, cen_maxima = 0;
+  om_census_layout(&cen_counts, &cen_extremes, &cen_maxima);
+  std::vector<uint64_t> cen_n(cen_counts);  // exactly the layout's sizes: an overrun is a report
+  std::vector<float> cen_x(cen_extremes);
   for (uint32_t scene = 0; scene < 20; ++scene) {
     for (int32_t iters : {0, 3, 33}) {
       frm_parameters q = p;
@@ -82,6 +93,10 @@ int main(int argc, char** argv) {
         std::vector<uint8_t> two_rows((size_t)2 * w * 4);
         if (om_render((const uint8_t*)&q, w, h, 32, 0, 0, rows, 2, threads, two_rows.data(), c, nullptr, nullptr))
           return fail("om_render rows");
+        // the census: per-thread accumulation merged under the job's mutex, both march kinds
+        if (om_render_census((const uint8_t*)&q, w, h, 32, 0, 0, nullptr, h, threads, rgba.data(), c, nullptr, nullptr,
+                             nullptr, cen_n.data(), cen_x.data()))
+          return fail("om_render_census");
       }
     }
   }
@@ -96,6 +111,9 @@ int main(int argc, char** argv) {
     for (int mode = 0; mode < 2; ++mode)
       if (om_scene_de((const uint8_t*)&q, 0, mode, pts.data(), (uint32_t)d.size(), d.data(), col.data(), counts))
         return fail("om_scene_de");
+    if (om_scene_de_census((const uint8_t*)&q, 0, 0, pts.data(), (uint32_t)d.size(), d.data(), col.data(), counts,
+                           cen_n.data(), cen_x.data()))
+      return fail("om_scene_de_census");
   }
   for (int i = 0; i < 64; ++i) {
     a[i] = (i - 32) * 0.37f;

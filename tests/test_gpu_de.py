@@ -3,6 +3,7 @@ estimator + colour evaluated on the device equal the CPU oracle bit for bit."""
 import numpy as np
 import pytest
 
+import edge_cases as ec
 import frm
 from helpers import params_for, same_bits
 
@@ -93,6 +94,42 @@ def test_mandelbulb_tame_and_exact_paths(gpu_renderer_factory, oracle):
                 assert same_bits(d, rd), f"N={iters}: {np.sum(~((d.view(np.uint32) == rd.view(np.uint32)) | (np.isnan(d) & np.isnan(rd))))} mismatches"
 
 
+@pytest.mark.parametrize("case", ec.POINT_CASES, ids=ec.POINT_CASE_IDS)
+def test_scene_de_bit_exact_at_edge_counts(gpu_renderer_factory, oracle, case):
+    """The point cases of tests/edge_cases.py: Koch where its scale reaches 2^125 and inf (NaN,
+    inf and zero distances), Menger where its distances go subnormal, the Mandelbulb at N = 64 and
+    200 and at powers 4 and 9 over waves that are all tame, all exact and mixed at the tame test's
+    two boundaries (|p| around 2^-13, a component around 2^-60), and the deep points whose dr
+    passes 2^125 or overflows (subnormal and x / inf distances). test_edge_census.py asserts on
+    the CPU that each set meets those events."""
+    pts = ec.point_set(case.points)
+    p = case.params()
+    with gpu_renderer_factory() as r:
+        r.update_parameters_buffer(p)
+        d, col = r.eval_scene(pts)
+    rd, rcol, _ = oracle.scene_de(p, pts)
+    bad = ~((d.view(np.uint32) == rd.view(np.uint32)) | (np.isnan(d) & np.isnan(rd)))
+    assert not bad.any(), f"{case.name}: {bad.sum()} DE mismatches, e.g. p={pts[bad][:2]} gpu={d[bad][:2]} cpu={rd[bad][:2]}"
+    assert same_bits(col, rcol), f"{case.name}: colour mismatch"
+
+
+@pytest.mark.parametrize("name", ["div", "sqrt"])
+def test_div_and_sqrt_over_the_whole_type(gpu, oracle, name):
+    """div on random finite encodings (subnormals included), the cross product of the special
+    values and quotients around 2^-126, FLT_MAX and the ties between subnormals; sqrt on random
+    non-negative encodings, subnormals and every power of two's neighbourhood. The oracle's own
+    results equal numpy's float32 `/` and sqrt on these arrays (test_edge_census.py)."""
+    if name == "div":
+        a, b = ec.div_whole_type_inputs()
+    else:
+        a, b = ec.sqrt_whole_type_inputs(), None
+    got = gpu.eval_math(name, a, b)
+    ref = oracle.math_fn(name, a, b)
+    bad = ~((got.view(np.uint32) == ref.view(np.uint32)) | (np.isnan(got) & np.isnan(ref)))
+    assert not bad.any(), (f"{name}: {bad.sum()} mismatches, e.g. a={a[bad][:3]} b={None if b is None else b[bad][:3]} "
+                           f"gpu={got[bad][:3]} cpu={ref[bad][:3]}")
+
+
 def _tame(rng, n, lo=-60, hi=40, zeros=True):
     """Values 0 (if zeros) or +-2^e * mantissa with e in [lo, hi): the tame operand range."""
     mag = np.clip(np.exp2(rng.uniform(lo, hi, n)), 2.0 ** lo, 2.0 ** hi)
@@ -120,7 +157,10 @@ def _fast_inputs(name, rng):
             b = np.concatenate([b, [-3.0, 5.0, -5.0, 2.0 ** 40, 2.0 ** -60]])
         else:  # the numerator is never -0 there (frm_fast.h)
             a[a == 0] = 0.0
-        return "div", a, b
+        # the ends of the stated domain: operands within 3 encodings of 2^-60 and 2^40, the extreme
+        # quotients 2^40 / 2^-60 and 2^-60 / 2^40 among them
+        ea, eb = ec.div_tame_edge_inputs()
+        return "div", np.concatenate([a, ea]), np.concatenate([b, eb])
     if name in ("sin_small", "cos_small"):
         lim = 2.0 ** 20  # sincos_small is sincos_'s |x| <= 2^20 branch (frm_math.h)
         a = np.concatenate([rng.uniform(-30, 30, n), rng.uniform(-lim, lim, n // 4),
