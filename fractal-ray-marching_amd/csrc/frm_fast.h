@@ -13,6 +13,13 @@
 //    profiles/round5/hw_exact.json): the correctly rounded reciprocal in three instructions.
 //  * a / b: a * RN(1 / b) corrected once (Markstein), in place of LLVM's division sequence
 //    (v_div_scale, v_rcp, Newton steps, v_div_fmas, v_div_fixup).
+//  * a / b with special values: div_fix / div_by_rcp_fix are that division ended by v_div_fixup_f32,
+//    the compiler's own last instruction, which supplies a / b for zeros, infinities and NaNs per
+//    lane (7 instructions for the compiler's 11; 4 per quotient once RN(1 / b) is shared). Domain
+//    for finite non-zero operands: |b| in [2^-100, 2^100], |a| >= 2^-102, |a / b| in [2^-125,
+//    2^125]. RN(1 / b) comes from the exhaustive probe, the correction from Markstein's theorem
+//    (exact remainder, normal quotient), the special values from the instruction's definition.
+//    Used by the last normal tap's normalize (frm_scene.h normalize_rsq).
 //  * log2 / exp2: the special-value selects are dead for positive normal finite inputs /
 //    finite exponents; the exponent split of log2 and the scaling of exp2 are integer
 //    arithmetic on the encodings where the operand (log2) / result (exp2) is normal.
@@ -86,6 +93,36 @@ __device__ __forceinline__ float div_by_rcp(float a, float b, float y) {
   const float r = fmaf(fmaf(-b, q, a), y, q);
   return (a == 0.0f) ? a : r;
 }
+
+// The last instruction of the compiler's own division, v_div_fixup_f32(q, b, a): the IEEE result of
+// a / b where either operand is a zero, an infinity or a NaN (0 / 0, x / 0, x / inf, ... with the
+// generic sequence's own NaN encodings: it ends in this very instruction on the same a and b), and
+// q with the sign of a / b for every other pair. A division built on it handles those operands per
+// lane, for nothing; only finite non-zero operands need a domain.
+__device__ __forceinline__ float div_fixup_(float q, float b, float a) {
+#if __has_builtin(__builtin_amdgcn_div_fixupf)
+  return __builtin_amdgcn_div_fixupf(q, b, a);
+#else
+  const float aa = fabsf(a), ab = fabsf(b);
+  const float inf = __builtin_inff();
+  return (aa > 0.0f && aa < inf && ab > 0.0f && ab < inf) ? q : a / b;
+#endif
+}
+
+// a / b from y = RN(1 / b): q = RN(a y) is within an ulp of a / b, one Markstein correction
+// RN(q + RN(a - b q) y) is RN(a / b), and div_fixup_ supplies the special values. Correct where
+//   * |b| is in [2^-100, 2^100] (rcp_rn is RN(1 / b) up to 2^125: exhaustive probe, above), or b is
+//     +-0, +-inf or NaN;
+//   * a is +-0, +-inf, NaN, or finite with |a| >= 2^-102 and 2^-125 <= |a / b| <= 2^125: the
+//     quotient is then normal, and the remainder a - b q, a multiple of ulp(b) ulp(q) >=
+//     2^-47 |a| >= 2^-149, is representable, so the fma computes it exactly (Markstein's theorem
+//     needs nothing else; subnormals are not flushed in this build).
+// normalize_rsq (frm_scene.h) divides inside that region: |b| in [2^-48, 2^63], |a| >= 2^-62.
+__device__ __forceinline__ float div_by_rcp_fix(float a, float b, float y) {
+  const float q = a * y;
+  return div_fixup_(fmaf(fmaf(-b, q, a), y, q), b, a);
+}
+__device__ __forceinline__ float div_fix(float a, float b) { return div_by_rcp_fix(a, b, rcp_rn(b)); }
 
 // v ^ (m & 0x80000000) in one v_bitop3_b32 (truth table 0x6c: (src0 & src2) ^ src1); left to
 // itself the compiler sometimes splits it into v_and + v_xor

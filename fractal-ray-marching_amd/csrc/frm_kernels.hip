@@ -69,6 +69,12 @@ __global__ __launch_bounds__(256) void eval_math(int fn, const float* a, const f
     case 17: r = log2_tame(x); break;
     case 18: r = exp2_tame(x); break;
     case 19: r = log_posnormal(x); break;
+    // (20: srgb_encode, the default arm)
+    case 21: r = div_fix(x, y); break;
+    case 22: r = normalize_wave(mk(x, y, y)).x; break;  // the last tap's guarded normalize
+    case 23: r = normalize_wave(mk(x, y, y)).y; break;
+    case 24: r = normalize(mk(x, y, y)).x; break;
+    case 25: r = normalize(mk(x, y, y)).y; break;
     default: r = (float)encode_srgb(x, kSrgbThresholds); break;
 #else
     default: r = x; break;

@@ -880,7 +880,11 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
     phase = ev_hit ? kTap0 : (tap ? phase + 1u : phase);  // after the last tap: kShadow
     if (tap && k == kTap3 - kTap0) {  // normal, then the shadow ray toward the sun
       FRM_SUB_BEGIN();
+#if defined(__HIP_DEVICE_COMPILE__)  // one reciprocal for the three quotients when the lanes allow it (same bits)
+      const v3 n = normalize_wave(nsum);
+#else
       const v3 n = normalize(nsum);
+#endif
       const v3 hp = ray_at(o, t, d);
       if constexpr (RES) {  // read by another wave's shading, maybe on another XCD (ring_flush)
         coherent_store(&geom[pix], make_float4(t, n.x, n.y, n.z));

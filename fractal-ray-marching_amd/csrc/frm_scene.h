@@ -363,6 +363,27 @@ __device__ __forceinline__ bool length_wide(v3 a) {
   return __float_as_uint(dot(a, a)) - kLo > kHi - kLo;
 }
 
+// normalize() through sqrt_rsq, one correctly rounded reciprocal of the length and three corrected
+// products (div_by_rcp_fix) in place of the correctly rounded sqrt and three whole divisions: same
+// bits when dot(a, a) lies in [2^-96, 2^126] (the length l in [2^-48, 2^63]) and every component
+// has a magnitude >= 2^-62 (the quotients, at most 1, are then >= 2^-125: normal). normalize_wide:
+// whether a lane lies outside that (a zero or tiny component, a zero-length sum and its NaN normal,
+// inf, NaN: a NaN component fails through its NaN dot product); such a wave takes normalize().
+__device__ __forceinline__ bool normalize_wide(v3 a) {
+  float m;
+  asm("v_min3_f32 %0, |%1|, |%2|, |%3|" : "=v"(m) : "v"(a.x), "v"(a.y), "v"(a.z));
+  return length_wide(a) | !(m >= 0x1p-62f);
+}
+__device__ __forceinline__ v3 normalize_rsq(v3 a) {
+  const float l = length_rsq(a);
+  const float y = rcp_rn(l);
+  return mk(div_by_rcp_fix(a.x, l, y), div_by_rcp_fix(a.y, l, y), div_by_rcp_fix(a.z, l, y));
+}
+// normalize() for the active lanes of a wave, by the fast path when all of them allow it
+__device__ __forceinline__ v3 normalize_wave(v3 a) {
+  return ballot(normalize_wide(a)) == 0 ? normalize_rsq(a) : normalize(a);
+}
+
 #endif
 
 

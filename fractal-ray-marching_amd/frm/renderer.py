@@ -176,7 +176,11 @@ class Renderer:
                "cos_small": 14, "acos_dev": 15, "atan2_tame": 16, "log2_tame": 17,
                "exp2_tame": 18, "log_posnormal": 19,
                # the sRGB store's code (frm_scene.h encode_srgb), as a float
-               "srgb_encode": 20}
+               "srgb_encode": 20,
+               # the division ended by v_div_fixup (frm_fast.h div_fix) and the last tap's normalize
+               # of (a, b, b), guarded (normalize_wave) and plain
+               "div_fix": 21, "normalize_guarded_x": 22, "normalize_guarded_y": 23,
+               "normalize_x": 24, "normalize_y": 25}
 
     def eval_scene(self, points):
         pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)

@@ -320,7 +320,13 @@ enum {
   FRM_MATH_ATAN2_TAME = 16, FRM_MATH_LOG2_TAME = 17, FRM_MATH_EXP2_TAME = 18,
   FRM_MATH_LOG_POSNORMAL = 19,
   /* the Rgba8UnormSrgb store's 8-bit code of a linear value (as a float; csrc/frm_scene.h) */
-  FRM_MATH_SRGB_ENCODE = 20
+  FRM_MATH_SRGB_ENCODE = 20,
+  /* the division ended by v_div_fixup (csrc/frm_fast.h div_fix), and the x / y component of the
+     march's last-tap normalize of (a, b, b): guarded (per wave the reciprocal-based form when every
+     lane allows it, csrc/frm_scene.h normalize_wave) and plain */
+  FRM_MATH_DIV_FIX = 21, FRM_MATH_NORMALIZE_GUARDED_X = 22, FRM_MATH_NORMALIZE_GUARDED_Y = 23,
+  FRM_MATH_NORMALIZE_X = 24, FRM_MATH_NORMALIZE_Y = 25,
+  FRM_MATH_LAST = 25
 };
 int frm_eval_scene(frm_ctx* ctx, const float* points, uint32_t n, float* out_distance,
                    float* out_color);
