@@ -75,6 +75,10 @@ struct Slot {
   bool fb_read_pending[2] = {false, false};
   uint32_t fb_idx = 0;
   uint8_t* fb = nullptr;
+  // supersampling (frm_set_supersampling, factor > 1): the resolved image of fbs[i], what the
+  // presentation paths read; alternating with the framebuffers, so fb_read[i] covers its readers too
+  uint8_t* res[2] = {nullptr, nullptr};
+  size_t res_cap[2] = {0, 0};
   unsigned int* queue = nullptr;
   uint8_t* records = nullptr;  // persistent kernel scratch (ShadeGeom[cap] then ShadeTail[cap]), grown on demand
   size_t records_cap = 0;
@@ -208,7 +212,9 @@ struct frm_ctx {
   // the pool (release threshold: never) for the next size change.
   hipMemPool_t pool = nullptr;
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-  uint32_t width = 0, height = 0;
+  uint32_t width = 0, height = 0;  // the internal render size: supersample x the output size
+  uint32_t supersample = 1;        // frm_set_supersampling
+  uint32_t out_width = 0, out_height = 0;  // frm_resize's size: what the presentation paths show
   Slot slots[FRM_MAX_FRAMES_IN_FLIGHT];
   uint32_t nslots = 1;
   uint32_t next_slot = 0;  // slot of the next launch
@@ -274,6 +280,13 @@ int not_on_group(frm_ctx* ctx, const char* what) {
   return fail(ctx, FRM_ERR_UNSUPPORTED, "%s: not available on a group context (frm_config.device_count)", what);
 }
 
+int not_supersampled(frm_ctx* ctx, const char* what) {
+  return fail(ctx, FRM_ERR_UNSUPPORTED,
+              "%s: not available on a supersampled context (frm_set_supersampling); render the bands at the "
+              "internal size on a plain context and call frm_resolve",
+              what);
+}
+
 // Device memory of the context pool, allocated / released in the order of stream s: a block
 // released on s is reused only by work ordered after everything enqueued on s before the release.
 int dev_alloc(frm_ctx* ctx, void** p, size_t bytes, hipStream_t s) {
@@ -309,6 +322,35 @@ int select_fb(frm_ctx* ctx, Slot& sl, uint32_t i) {
     sl.fb_read_pending[i] = false;
   }
   return FRM_OK;
+}
+
+// The resolved image that goes with the slot's current framebuffer, for an output frame of `bytes`,
+// grown on the slot stream like the framebuffer (ensure_fb; select_fb has ordered its readers).
+int ensure_res(frm_ctx* ctx, Slot& sl, size_t bytes) {
+  const uint32_t i = sl.fb_idx;
+  if (sl.res_cap[i] >= bytes) return FRM_OK;
+  int rc = dev_release(ctx, sl.res[i], sl.stream);
+  if (rc) return rc;
+  sl.res[i] = nullptr;
+  sl.res_cap[i] = 0;
+  if ((rc = dev_alloc(ctx, (void**)&sl.res[i], bytes, sl.stream))) return rc;
+  sl.res_cap[i] = bytes;
+  return FRM_OK;
+}
+// The frame of the slot's current framebuffer at the output size, on the slot stream, after the
+// frame is complete there: the box resolve of a supersampled context. The slot's `done` event is
+// recorded again, so that it covers the resolved image.
+int resolve_frame(frm_ctx* ctx, Slot& sl) {
+  if (ctx->supersample == 1u) return FRM_OK;
+  const size_t bytes = (size_t)ctx->out_width * ctx->out_height * 4u;
+  if (int rc = ensure_res(ctx, sl, bytes + bytes / 4u)) return rc;
+  FRM_HIP(ctx, launch_resolve(sl.fb, sl.res[sl.fb_idx], ctx->out_width, ctx->out_height, ctx->supersample, sl.stream));
+  FRM_HIP(ctx, hipEventRecord(sl.done, sl.stream));
+  return FRM_OK;
+}
+// What the presentation paths read of a slot: out_width x out_height texels.
+const uint8_t* shown(const frm_ctx* ctx, const Slot& sl) {
+  return ctx->supersample > 1u ? sl.res[sl.fb_idx] : sl.fb;
 }
 
 uint32_t num_bands(uint32_t height, uint32_t band_rows) { return (height + band_rows - 1) / band_rows; }
@@ -703,6 +745,7 @@ int group_render(frm_ctx* ctx, frm_stats* stats) {
   FRM_HIP(ctx, hipSetDevice(ctx->device));
   FRM_HIP(ctx, launch_unshuffle(gs.gathered, G.stride, sl.fb, ctx->width, ctx->height, G.band_rows, n, s0));
   FRM_HIP(ctx, hipEventRecord(sl.done, s0));
+  if ((rc = resolve_frame(ctx, sl))) return rc;
   ctx->last_slot = si;
   ctx->render_seq = sl.seq;
   ctx->render_params = ctx->params;
@@ -748,6 +791,7 @@ uint32_t ring_size(const frm_ctx* ctx) { return ctx->nslots >= 3 ? 4u : 2u; }
 // Whether frm_render(ctx, NULL) goes through the ring.
 bool ring_eligible(const frm_ctx* ctx) {
   if (!ctx->ring_enabled || ctx->group || ctx->bands_only || ctx->reloaded || ctx->nslots < 2) return false;
+  if (ctx->supersample > 1u) return false;  // ring frames are not resolved
   const uint64_t npix = (uint64_t)ctx->width * ctx->height;
   if (kernel_for(ctx, npix) != kKernelPersistent || npix > (1ull << 28)) return false;
   // a ring's service waves give up after kRingWatchdogTicks (2 s) without progress: keep the
@@ -1300,7 +1344,7 @@ int frm_destroy(frm_ctx* ctx) {
     Slot& sl = ctx->slots[i];
     // pool blocks back to the pool (every stream is idle), then the pool itself below
     if (ctx->stream)
-      for (void* b : {(void*)sl.fbs[0], (void*)sl.fbs[1], (void*)sl.records, (void*)sl.sched_iota, (void*)sl.sched_order,
+      for (void* b : {(void*)sl.fbs[0], (void*)sl.fbs[1], (void*)sl.res[0], (void*)sl.res[1], (void*)sl.records, (void*)sl.sched_iota, (void*)sl.sched_order,
                       (void*)sl.sched_keys, sl.sched_temp, (void*)sl.present_dev})
         if (b) (void)hipFreeAsync(b, ctx->stream);
     if (sl.queue) (void)hipFree(sl.queue);
@@ -1326,14 +1370,11 @@ int frm_destroy(frm_ctx* ctx) {
   return FRM_OK;
 }
 
-int frm_resize(frm_ctx* ctx, uint32_t width, uint32_t height) {
-  if (!ctx) return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  if (width == 0 || height == 0 || width > FRM_MAX_DIMENSION || height > FRM_MAX_DIMENSION)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "frame size %ux%u outside [1, %u]^2", width, height,
-                FRM_MAX_DIMENSION);
+// The internal render size (supersample x the output size): everything that renders follows it.
+static int resize_render(frm_ctx* ctx, uint32_t width, uint32_t height) {
   if (Group* G = ctx->group) {  // every member follows; the band geometry of the new size
     for (uint32_t r = 1; r < G->n; ++r)
-      if (int rc = frm_resize(G->sub[r], width, height)) return relay(ctx, G->sub[r], rc);
+      if (int rc = resize_render(G->sub[r], width, height)) return relay(ctx, G->sub[r], rc);
     G->band_rows = group_band_rows(height, G->n);
     G->stride = (size_t)band_local_rows(height, G->band_rows, 0, G->n) * width * 4u;
   }
@@ -1361,6 +1402,85 @@ int frm_resize(frm_ctx* ctx, uint32_t width, uint32_t height) {
   // no frame of the new size yet: frm_read_frame_async / frm_present_async refuse until the next
   // frm_render (tickets issued before keep their frames)
   ctx->render_seq = 0;
+  return FRM_OK;
+}
+
+// An output size and a supersampling factor (checked by the callers): the render size is their
+// product. The slot that frm_read_frame sees before the next frm_render gets its resolved image.
+static int apply_size(frm_ctx* ctx, uint32_t width, uint32_t height, uint32_t factor) {
+  int rc = resize_render(ctx, factor * width, factor * height);
+  if (rc) return rc;
+  ctx->supersample = factor;
+  if (Group* G = ctx->group)
+    for (uint32_t r = 1; r < G->n; ++r) G->sub[r]->supersample = factor;
+  ctx->out_width = width;
+  ctx->out_height = height;
+  if (factor > 1u) {
+    Slot& sl = ctx->slots[ctx->last_slot];
+    const size_t bytes = (size_t)width * height * 4u;
+    if ((rc = select_fb(ctx, sl, sl.fb_idx)) || (rc = ensure_res(ctx, sl, bytes + bytes / 4u))) return rc;
+  }
+  return FRM_OK;
+}
+
+int frm_resize(frm_ctx* ctx, uint32_t width, uint32_t height) {
+  if (!ctx) return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  const uint32_t limit = FRM_MAX_DIMENSION / ctx->supersample;
+  if (width == 0 || height == 0 || width > limit || height > limit)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "frame size %ux%u outside [1, %u]^2 (supersampling %u)", width, height,
+                limit, ctx->supersample);
+  return apply_size(ctx, width, height, ctx->supersample);
+}
+
+int frm_set_supersampling(frm_ctx* ctx, uint32_t factor) {
+  if (!ctx) return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (factor == 0 || factor > FRM_MAX_SUPERSAMPLE)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "supersampling factor %u outside [1, %u]; factor not changed", factor,
+                FRM_MAX_SUPERSAMPLE);
+  if (ctx->out_width) {
+    const uint32_t limit = FRM_MAX_DIMENSION / factor;
+    if (ctx->out_width > limit || ctx->out_height > limit)
+      return fail(ctx, FRM_ERR_INVALID_ARGUMENT,
+                  "supersampling factor %u: the %ux%u frame would render above %u texels a side; factor not changed",
+                  factor, ctx->out_width, ctx->out_height, FRM_MAX_DIMENSION);
+    if (factor == ctx->supersample) return FRM_OK;
+    return apply_size(ctx, ctx->out_width, ctx->out_height, factor);
+  }
+  ctx->supersample = factor;
+  if (Group* G = ctx->group)
+    for (uint32_t r = 1; r < G->n; ++r) G->sub[r]->supersample = factor;
+  return FRM_OK;
+}
+
+int frm_get_supersampling(const frm_ctx* ctx, uint32_t* out_factor) {
+  if (!ctx || !out_factor) return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "ctx/out_factor is NULL");
+  *out_factor = ctx->supersample;
+  return FRM_OK;
+}
+
+int frm_resolve(frm_ctx* ctx, const uint8_t* dev_src, size_t src_bytes, uint32_t out_width, uint32_t out_height,
+                uint32_t factor, uint8_t* dev_dst, size_t dst_bytes, void* stream) {
+  if (!ctx || !dev_src || !dev_dst) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "ctx/dev_src/dev_dst is NULL");
+  if (factor == 0 || factor > FRM_MAX_SUPERSAMPLE)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "supersampling factor %u outside [1, %u]", factor, FRM_MAX_SUPERSAMPLE);
+  const uint32_t limit = FRM_MAX_DIMENSION / factor;
+  if (out_width == 0 || out_height == 0 || out_width > limit || out_height > limit)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "output size %ux%u outside [1, %u]^2 (factor %u)", out_width, out_height,
+                limit, factor);
+  const uintptr_t sa = reinterpret_cast<uintptr_t>(dev_src), da = reinterpret_cast<uintptr_t>(dev_dst);
+  if (sa % 4u || da % 4u) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "dev_src / dev_dst not 4-byte aligned");
+  const size_t dst_need = (size_t)out_width * out_height * 4u, src_need = dst_need * factor * factor;
+  if (src_bytes < src_need)
+    return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "src holds %zu bytes, %ux%u texels need %zu", src_bytes,
+                factor * out_width, factor * out_height, src_need);
+  if (dst_bytes < dst_need)
+    return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "dst holds %zu bytes, the frame needs %zu", dst_bytes, dst_need);
+  if (sa < da + dst_need && da < sa + src_need)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "dev_src and dev_dst overlap");
+  FRM_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = ring_leave(ctx)) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  FRM_HIP(ctx, launch_resolve(dev_src, dev_dst, out_width, out_height, factor, s));
   return FRM_OK;
 }
 
@@ -1406,7 +1526,7 @@ int frm_render(frm_ctx* ctx, frm_stats* stats) {
     FRM_HIP(ctx, hipEventRecord(ctx->ev_start, s));
   }
   rc = launch(ctx, a, s);
-  if (rc) return rc;
+  if (rc || (rc = resolve_frame(ctx, sl))) return rc;
   ctx->last_slot = si;
   ctx->render_seq = sl.seq;
   ctx->render_params = ctx->params;
@@ -1428,13 +1548,13 @@ int frm_render(frm_ctx* ctx, frm_stats* stats) {
 int frm_read_frame(frm_ctx* ctx, uint8_t* dst, size_t dst_bytes) {
   if (!ctx || !dst) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "ctx/dst is NULL");
   if (!ctx->width) return fail(ctx, FRM_ERR_NOT_READY, "frm_resize has not been called");
-  size_t need = (size_t)ctx->width * ctx->height * 4u;
+  size_t need = (size_t)ctx->out_width * ctx->out_height * 4u;
   if (dst_bytes < need)
     return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "dst holds %zu bytes, frame needs %zu", dst_bytes, need);
   FRM_HIP(ctx, hipSetDevice(ctx->device));
   if (int rc = ring_materialize(ctx)) return rc;
   const Slot& sl = ctx->slots[ctx->last_slot];  // the frame of the last frm_render
-  FRM_HIP(ctx, hipMemcpyAsync(dst, sl.fb, need, hipMemcpyDeviceToHost, sl.stream));
+  FRM_HIP(ctx, hipMemcpyAsync(dst, shown(ctx, sl), need, hipMemcpyDeviceToHost, sl.stream));
   FRM_HIP(ctx, hipStreamSynchronize(sl.stream));
   return FRM_OK;
 }
@@ -1460,7 +1580,7 @@ int frm_present(frm_ctx* ctx, uint32_t out_width, uint32_t out_height, uint32_t 
     FRM_HIP(ctx, hipMalloc(&ctx->present_buf, need));
     ctx->present_cap = need;
   }
-  FRM_HIP(ctx, launch_blit(sl.fb, ctx->width, ctx->height, ctx->present_buf, out_width, out_height, flags,
+  FRM_HIP(ctx, launch_blit(shown(ctx, sl), ctx->out_width, ctx->out_height, ctx->present_buf, out_width, out_height, flags,
                            sl.stream));
   FRM_HIP(ctx, hipMemcpyAsync(dst, ctx->present_buf, need, hipMemcpyDeviceToHost, sl.stream));
   FRM_HIP(ctx, hipStreamSynchronize(sl.stream));
@@ -1515,7 +1635,7 @@ int frm_read_frame_async(frm_ctx* ctx, uint64_t* out_ticket) {
   Slot& sl = ctx->slots[ctx->last_slot];  // the frame of the last frm_render
   int rc = copy_stream_after_render(ctx, sl);
   if (rc) return rc;
-  return readback_async(ctx, sl, sl.fb, (size_t)ctx->width * ctx->height * 4u, out_ticket);
+  return readback_async(ctx, sl, shown(ctx, sl), (size_t)ctx->out_width * ctx->out_height * 4u, out_ticket);
 }
 
 int frm_present_async(frm_ctx* ctx, uint32_t out_width, uint32_t out_height, uint32_t flags, uint64_t* out_ticket) {
@@ -1539,7 +1659,7 @@ int frm_present_async(frm_ctx* ctx, uint32_t out_width, uint32_t out_height, uin
     if ((rc = dev_alloc(ctx, (void**)&sl.present_dev, need, sl.rb_stream))) return rc;
     sl.present_dev_cap = need;
   }
-  FRM_HIP(ctx, launch_blit(sl.fb, ctx->width, ctx->height, sl.present_dev, out_width, out_height, flags,
+  FRM_HIP(ctx, launch_blit(shown(ctx, sl), ctx->out_width, ctx->out_height, sl.present_dev, out_width, out_height, flags,
                            sl.rb_stream));
   return readback_async(ctx, sl, sl.present_dev, need, out_ticket);
 }
@@ -1642,6 +1762,7 @@ int frm_render_bands(frm_ctx* ctx, uint8_t* dev_dst, size_t dst_bytes, uint32_t 
   int rc = ensure_ready(ctx);
   if (rc) return rc;
   if (ctx->group) return not_on_group(ctx, "frm_render_bands");
+  if (ctx->supersample > 1u) return not_supersampled(ctx, "frm_render_bands");
   if (!dev_dst || band_rows == 0 || band_stride == 0)
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "invalid dst or band geometry");
   uint32_t rows = band_local_rows(ctx->height, band_rows, first_band, band_stride);
@@ -1662,6 +1783,7 @@ int frm_render_bands_batch(frm_ctx* ctx, uint32_t count, const frm_parameters* p
                            void* stream, uint64_t* dev_counters) {
   if (!ctx) return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "ctx is NULL");
   if (ctx->group) return not_on_group(ctx, "frm_render_bands_batch");
+  if (ctx->supersample > 1u) return not_supersampled(ctx, "frm_render_bands_batch");
   if (!ctx->width) return fail(ctx, FRM_ERR_NOT_READY, "frm_resize has not been called");
   if (!params || !dev_dst || count == 0 || count > FRM_MAX_BATCH || band_rows == 0 || band_stride == 0)
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "invalid batch (count %u, at most %u) or band geometry", count,
@@ -1747,6 +1869,7 @@ int frm_unshuffle_bands(frm_ctx* ctx, const uint8_t* dev_src, size_t rank_stride
                         size_t dst_bytes, uint32_t band_rows, uint32_t ranks, void* stream) {
   if (!ctx || !dev_src || !dev_dst || band_rows == 0 || ranks == 0)
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "invalid unshuffle arguments");
+  if (ctx->supersample > 1u) return not_supersampled(ctx, "frm_unshuffle_bands");
   if (!ctx->width) return fail(ctx, FRM_ERR_NOT_READY, "frm_resize has not been called");
   size_t need = (size_t)ctx->width * ctx->height * 4u;
   if (dst_bytes < need)

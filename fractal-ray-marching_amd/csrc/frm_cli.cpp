@@ -9,6 +9,11 @@
 //              [--simple] [--sphere] [--out file.ppm | pattern_%04d.ppm]
 //              [--frames F] [--dt S] [--keys BITS] [--orbit RAD_PER_S]
 //              [--lock-yaw 0..4] [--lock-pitch] [--time-factor X] [--gpus N] [--batch B]
+//              [--ssaa K]
+// With --ssaa K (1..4) every frame is rendered with K x K samples per pixel and resolved in linear
+// light (frm_set_supersampling); W x H stay the size of the written frames, the work counters in
+// the JSON lines are those of the (K*W) x (K*H) frame rendered. With --batch the context stays plain
+// at that size and each frame goes through frm_resolve before it is copied to the host.
 // With --batch B (one context) the fly-through's frames are rendered B per launch
 // (frm_render_bands_batch: one work queue for B frames whose camera and, for the Mandelbulb,
 // time differ), so a launch's tail is paid once per B frames; the frames' bytes are the same.
@@ -63,7 +68,7 @@ static int write_ppm(const char* out, uint32_t fr, const uint8_t* rgba, uint32_t
 // the launch's, reported per launch.
 static int render_batched(frm_ctx* ctx, frm_parameters p, frm_camera cam, frm_timing timing, uint32_t keys,
                           float dt, uint32_t frames, uint32_t batch, uint32_t width, uint32_t height,
-                          const char* out) {
+                          uint32_t ssaa, const char* out) {
   std::vector<frm_parameters> ps(frames);
   std::vector<frm_camera> cams(frames);
   for (uint32_t fr = 0; fr < frames; ++fr) {
@@ -75,36 +80,44 @@ static int render_batched(frm_ctx* ctx, frm_parameters p, frm_camera cam, frm_ti
     ps[fr] = p;
     cams[fr] = cam;
   }
-  const size_t fb = (size_t)width * height * 4;
-  uint8_t* dev = nullptr;
+  // the context renders ssaa x the output size; `width` x `height` frames of `ofb` bytes are written
+  const uint32_t rh = ssaa * height;
+  const size_t ofb = (size_t)width * height * 4, fb = ofb * ssaa * ssaa;
+  uint8_t *dev = nullptr, *resolved = nullptr;
   uint64_t* dcnt = nullptr;
   hip_check(hipMalloc(&dev, fb * batch), "hipMalloc");
+  if (ssaa > 1) hip_check(hipMalloc(&resolved, ofb * batch), "hipMalloc");
   hip_check(hipMalloc(&dcnt, FRM_NUM_COUNTERS * sizeof(uint64_t)), "hipMalloc");
-  std::vector<uint8_t> host(fb * batch);
+  std::vector<uint8_t> host(ofb * batch);
   char name[4096];
   for (uint32_t g = 0; g < frames; g += batch) {
     const uint32_t n = frames - g < batch ? frames - g : batch;
     hip_check(hipMemset(dcnt, 0, FRM_NUM_COUNTERS * sizeof(uint64_t)), "hipMemset");
     const auto t0 = std::chrono::steady_clock::now();
-    check(frm_render_bands_batch(ctx, n, &ps[g], dev, fb * n, fb, height, 0, 1, nullptr, dcnt), ctx,
+    check(frm_render_bands_batch(ctx, n, &ps[g], dev, fb * n, fb, rh, 0, 1, nullptr, dcnt), ctx,
           "frm_render_bands_batch");
+    for (uint32_t b = 0; b < n && ssaa > 1; ++b)  // on the context's stream, after the launch
+      check(frm_resolve(ctx, dev + fb * b, fb, width, height, ssaa, resolved + ofb * b, ofb, nullptr), ctx,
+            "frm_resolve");
     check(frm_synchronize(ctx), ctx, "frm_synchronize");
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     uint64_t c[FRM_NUM_COUNTERS];
     hip_check(hipMemcpy(c, dcnt, sizeof(c), hipMemcpyDeviceToHost), "hipMemcpy");
-    hip_check(hipMemcpy(host.data(), dev, fb * n, hipMemcpyDeviceToHost), "hipMemcpy");
+    hip_check(hipMemcpy(host.data(), ssaa > 1 ? resolved : dev, ofb * n, hipMemcpyDeviceToHost), "hipMemcpy");
     for (uint32_t b = 0; b < n; ++b) {
       const uint32_t fr = g + b;
-      if (write_ppm(out, fr, &host[fb * b], width, height, name, sizeof(name))) return 1;
+      if (write_ppm(out, fr, &host[ofb * b], width, height, name, sizeof(name))) return 1;
       printf("{\"frame\": %u, \"out\": \"%s\", \"width\": %u, \"height\": %u, \"time\": %.6f, "
              "\"pos\": [%.5f, %.5f, %.5f], \"yaw\": %.5f, \"pitch\": %.5f, \"kernel_ms\": %.3f, "
-             "\"batch\": %u, \"launch_march_steps\": %llu, \"launch_hit_pixels\": %llu, \"gsteps_per_s\": %.3f}\n",
+             "\"batch\": %u, \"launch_march_steps\": %llu, \"launch_hit_pixels\": %llu, \"gsteps_per_s\": %.3f, "
+             "\"ssaa\": %u}\n",
              fr, name, width, height, ps[fr].time, cams[fr].position[0], cams[fr].position[1], cams[fr].position[2],
              cams[fr].yaw, cams[fr].pitch, ms / n, n, (unsigned long long)(c[2] + c[3]), (unsigned long long)c[1],
-             (double)(c[2] + c[3]) / (ms * 1e-3) / 1e9);
+             (double)(c[2] + c[3]) / (ms * 1e-3) / 1e9, ssaa);
     }
   }
   (void)hipFree(dev);
+  (void)hipFree(resolved);
   (void)hipFree(dcnt);
   frm_destroy(ctx);
   return 0;
@@ -121,6 +134,7 @@ int main(int argc, char** argv) {
   int lock_yaw = FRM_LOCK_YAW_NONE, lock_pitch = 0;
   uint32_t gpus = 0;  // 0: one GPU (--device); >= 1: a group context over devices 0..gpus-1
   uint32_t batch = 1;  // frames per launch (one context)
+  uint32_t ssaa = 1;   // samples per pixel and axis
   for (int i = 1; i < argc; ++i) {
     const char* a = argv[i];
     auto next = [&](void) -> const char* {
@@ -149,6 +163,16 @@ int main(int argc, char** argv) {
     else if (!strcmp(a, "--time-factor")) time_factor = (float)atof(next());
     else if (!strcmp(a, "--gpus")) gpus = (uint32_t)atoi(next());
     else if (!strcmp(a, "--batch")) batch = (uint32_t)atoi(next());
+    else if (!strcmp(a, "--ssaa")) {
+      const char* v = next();
+      char* end = nullptr;
+      const long k = strtol(v, &end, 10);
+      if (end == v || *end || k < 1 || k > (long)FRM_MAX_SUPERSAMPLE) {
+        fprintf(stderr, "frm_render: --ssaa %s outside [1, %u]\n", v, FRM_MAX_SUPERSAMPLE);
+        return 2;
+      }
+      ssaa = (uint32_t)k;
+    }
     else { fprintf(stderr, "unknown argument %s\n", a); return 2; }
   }
   frm_ctx* ctx = nullptr;
@@ -182,7 +206,13 @@ int main(int argc, char** argv) {
   frm_timing_init(&timing);
   timing.time_factor = time_factor;
   frm_parameters_update_camera_from(&p, &cam);
-  check(frm_resize(ctx, width, height), ctx, "frm_resize");
+  // --batch drives the bands itself: a plain context at the render size, resolved frame by frame
+  if (batch > 1) {
+    check(frm_resize(ctx, ssaa * width, ssaa * height), ctx, "frm_resize");
+  } else {
+    check(frm_set_supersampling(ctx, ssaa), ctx, "frm_set_supersampling");
+    check(frm_resize(ctx, width, height), ctx, "frm_resize");
+  }
   std::vector<uint8_t> rgba((size_t)width * height * 4);
   if (batch < 1 || batch > FRM_MAX_BATCH) {
     fprintf(stderr, "frm_render: --batch %u outside [1, %u]\n", batch, FRM_MAX_BATCH);
@@ -192,7 +222,7 @@ int main(int argc, char** argv) {
     fprintf(stderr, "frm_render: --batch renders on one GPU (frm_render_bands_batch is a per-device entry point)\n");
     return 2;
   }
-  if (batch > 1) return render_batched(ctx, p, cam, timing, keys, dt, frames, batch, width, height, out);
+  if (batch > 1) return render_batched(ctx, p, cam, timing, keys, dt, frames, batch, width, height, ssaa, out);
   for (uint32_t fr = 0; fr < frames; ++fr) {
     if (fr > 0) {  // initialized_app.rs:43-48, with a fixed frame time
       const float delta = frm_timing_update(&timing, &p, dt);
@@ -214,10 +244,10 @@ int main(int argc, char** argv) {
     fclose(f);
     printf("{\"frame\": %u, \"out\": \"%s\", \"width\": %u, \"height\": %u, \"time\": %.6f, "
            "\"pos\": [%.5f, %.5f, %.5f], \"yaw\": %.5f, \"pitch\": %.5f, \"kernel_ms\": %.3f, "
-           "\"march_steps\": %llu, \"hit_pixels\": %llu, \"gsteps_per_s\": %.3f}\n",
+           "\"march_steps\": %llu, \"hit_pixels\": %llu, \"gsteps_per_s\": %.3f, \"ssaa\": %u}\n",
            fr, name, width, height, p.time, cam.position[0], cam.position[1], cam.position[2], cam.yaw,
            cam.pitch, st.kernel_ms, (unsigned long long)st.march_steps, (unsigned long long)st.hit_pixels,
-           st.march_steps / (st.kernel_ms * 1e-3) / 1e9);
+           st.march_steps / (st.kernel_ms * 1e-3) / 1e9, ssaa);
   }
   frm_destroy(ctx);
   return 0;

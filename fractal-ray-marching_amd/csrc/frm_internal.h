@@ -240,6 +240,11 @@ hipError_t launch_blit(const uint8_t* src, uint32_t sw, uint32_t sh, uint8_t* ds
 hipError_t launch_unshuffle(const uint8_t* src, size_t rank_stride, uint8_t* dst, uint32_t width,
                             uint32_t height, uint32_t band_rows, uint32_t ranks,
                             hipStream_t stream);
+// Supersampling resolve (frm_set_supersampling, frm_resolve): src holds factor*dh rows of factor*dw
+// RGBA8 sRGB texels (pitch 4*factor*dw, 4-byte aligned), dst dh rows of dw; factor 1..4 (1: a copy
+// with alpha 255).
+hipError_t launch_resolve(const uint8_t* src, uint8_t* dst, uint32_t dw, uint32_t dh, uint32_t factor,
+                          hipStream_t stream);
 // Pixel scheduling (frm_sched.hip). With history, order = the local pixels 0..npix-1
 // (iota) by descending key[p], the cost key the last launch recorded for pixel p (stable,
 // one 8-bit radix pass); without, order = iota (row-major).

@@ -404,6 +404,88 @@ hipError_t launch_blit(const uint8_t* src, uint32_t sw, uint32_t sh, uint8_t* ds
   return hipGetLastError();
 }
 
+// Supersampling resolve (frm_set_supersampling, frm_resolve; DESIGN.md "Supersampling"): output
+// pixel (X, Y) is the box mean, in linear light, of the S x S texels of the Rgba8UnormSrgb source
+// under it, as a filtering sampler over that texture averages them: decode each code
+// (kSrgbDecode), add the S*S values in f32 row by row, left to right, divide by S*S (correctly
+// rounded; tests/ssaa_reference.py pins this order, other orders change a few codes per million
+// blocks) and store as the sRGB store does (encode_srgb). Alpha is 255.
+// One thread per output pixel, one wave per 64 consecutive pixels of an output row, so each of its
+// S source rows is one contiguous run of 64*S texels per wave. VEC: a lane reads its S texels of a
+// row with one load (uint2 / uint4; the source base must be 4*S-byte aligned, which with the
+// 4*S*dw pitch aligns every lane's load); otherwise dword loads (S = 3, or a 4-byte aligned source).
+template <uint32_t S, bool VEC>
+__global__ __launch_bounds__(256) void resolve_box(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
+                                                   uint32_t dw, uint32_t dh) {
+  __shared__ float dec[256], enc[256];
+  const uint32_t t = threadIdx.y * 64u + threadIdx.x;
+  dec[t] = kSrgbDecode[t];
+  enc[t] = kSrgbThresholds[t];
+  __syncthreads();
+  const uint32_t x = blockIdx.x * 64u + threadIdx.x, y = blockIdx.y * 4u + threadIdx.y;
+  if (x >= dw || y >= dh) return;
+  const size_t pitch = (size_t)S * dw;  // source texels per row
+  const uint32_t* p = src + (size_t)S * y * pitch + (size_t)S * x;
+  float r = 0.0f, g = 0.0f, b = 0.0f;
+#pragma unroll
+  for (uint32_t j = 0; j < S; ++j, p += pitch) {
+    uint32_t tx[S];
+    if constexpr (VEC && S == 2) {
+      const uint2 v = *reinterpret_cast<const uint2*>(p);
+      tx[0] = v.x, tx[1] = v.y;
+    } else if constexpr (VEC && S == 4) {
+      const uint4 v = *reinterpret_cast<const uint4*>(p);
+      tx[0] = v.x, tx[1] = v.y, tx[2] = v.z, tx[3] = v.w;
+    } else {
+#pragma unroll
+      for (uint32_t i = 0; i < S; ++i) tx[i] = p[i];
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < S; ++i) {
+      r = r + dec[tx[i] & 255u];
+      g = g + dec[(tx[i] >> 8) & 255u];
+      b = b + dec[(tx[i] >> 16) & 255u];
+    }
+  }
+  constexpr float n = (float)(S * S);
+  dst[(size_t)y * dw + x] = encode_srgb(r / n, enc) | (encode_srgb(g / n, enc) << 8) | (encode_srgb(b / n, enc) << 16) |
+                            (255u << 24);
+}
+
+// Factor 1: the texels themselves (encode_srgb(kSrgbDecode[k]) == k), alpha 255.
+__global__ __launch_bounds__(256) void resolve_copy(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
+                                                    size_t n) {
+  const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+  if (i < n) dst[i] = src[i] | (255u << 24);
+}
+
+template <uint32_t S>
+static void resolve_one(const uint8_t* src, uint8_t* dst, uint32_t dw, uint32_t dh, hipStream_t stream) {
+  const dim3 grid((dw + 63u) / 64u, (dh + 3u) / 4u), block(64, 4);
+  const bool vec = S != 3 && reinterpret_cast<uintptr_t>(src) % (4u * S) == 0;
+  if (vec)
+    hipLaunchKernelGGL((resolve_box<S, true>), grid, block, 0, stream, (const uint32_t*)src, (uint32_t*)dst, dw, dh);
+  else
+    hipLaunchKernelGGL((resolve_box<S, false>), grid, block, 0, stream, (const uint32_t*)src, (uint32_t*)dst, dw, dh);
+}
+
+hipError_t launch_resolve(const uint8_t* src, uint8_t* dst, uint32_t dw, uint32_t dh, uint32_t factor,
+                          hipStream_t stream) {
+  switch (factor) {
+    case 1: {
+      const size_t n = (size_t)dw * dh;
+      hipLaunchKernelGGL(resolve_copy, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, stream, (const uint32_t*)src,
+                         (uint32_t*)dst, n);
+      break;
+    }
+    case 2: resolve_one<2>(src, dst, dw, dh, stream); break;
+    case 3: resolve_one<3>(src, dst, dw, dh, stream); break;
+    case 4: resolve_one<4>(src, dst, dw, dh, stream); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
 hipError_t launch_unshuffle(const uint8_t* src, size_t rank_stride, uint8_t* dst, uint32_t width,
                             uint32_t height, uint32_t band_rows, uint32_t ranks,
                             hipStream_t stream) {

@@ -25,6 +25,7 @@ FRM_NUM_SCENES = 19
 FRM_MAX_FRAMES_IN_FLIGHT = 8
 FRM_MAX_DEVICES = 16
 FRM_MAX_BATCH = 32
+FRM_MAX_SUPERSAMPLE = 4
 FRM_DEFAULT_MAX_STEPS = 5000
 FRM_MAX_STEPS_LIMIT = 4194303
 FRM_MAX_NUM_ITERATIONS = 65536
@@ -113,6 +114,11 @@ SIGNATURES = [
     ("frm_create", ctypes.c_int, [_P(ctypes.c_void_p), _P(FrmConfig)]),
     ("frm_destroy", ctypes.c_int, [ctypes.c_void_p]),
     ("frm_resize", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]),
+    ("frm_set_supersampling", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
+    ("frm_get_supersampling", ctypes.c_int, [ctypes.c_void_p, _P(ctypes.c_uint32)]),
+    ("frm_resolve", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+      ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     ("frm_set_parameters", ctypes.c_int, [ctypes.c_void_p, _P(FrmParameters)]),
     ("frm_render", ctypes.c_int, [ctypes.c_void_p, _P(FrmStats)]),
     ("frm_read_frame", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),

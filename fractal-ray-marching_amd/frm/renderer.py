@@ -11,8 +11,9 @@ from . import _lib
 
 
 class Renderer:
-    def __init__(self, device=0, max_steps=0, flags=0, frames_in_flight=1, devices=None):
-        """devices: a list of HIP device ordinals for a GROUP context (frm_config.device_count):
+    def __init__(self, device=0, max_steps=0, flags=0, frames_in_flight=1, devices=None, supersampling=1):
+        """supersampling: samples per pixel and axis (frm_set_supersampling; 1 = off).
+        devices: a list of HIP device ordinals for a GROUP context (frm_config.device_count):
         every frame is row-tiled over them and gathered on devices[0] (RCCL, or device copies
         when a device repeats); the rest of the API is the same."""
         lib = _lib.load()
@@ -32,6 +33,13 @@ class Renderer:
         self.device = device
         self.frames_in_flight = max(1, frames_in_flight)
         self.width = self.height = 0
+        self.supersampling = 1
+        if supersampling != 1:
+            try:
+                self.set_supersampling(supersampling)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if self.ctx:
@@ -57,6 +65,27 @@ class Renderer:
     def resize(self, width, height):
         self._check(self._lib.frm_resize(self.ctx, width, height))
         self.width, self.height = width, height
+
+    def set_supersampling(self, factor):
+        """frm_set_supersampling: every frame is rendered at factor x the resize() size and box-resolved
+        in linear light; width/height, read_frame, present and tickets stay at the output size."""
+        self._check(self._lib.frm_set_supersampling(self.ctx, factor))
+        self.supersampling = int(factor)
+
+    # the internal render size: what trace(), pixel_keys() and set_pixel_keys() work on
+    @property
+    def render_width(self):
+        return self.width * self.supersampling
+
+    @property
+    def render_height(self):
+        return self.height * self.supersampling
+
+    def resolve(self, src_ptr, src_bytes, out_w, out_h, factor, dst_ptr, dst_bytes, stream=0):
+        """frm_resolve: box-resolve (factor*out_h) x (factor*out_w) RGBA8 sRGB texels at device pointer
+        src_ptr into out_h x out_w at dst_ptr, asynchronously on `stream` (0: the context's)."""
+        self._check(self._lib.frm_resolve(self.ctx, src_ptr, src_bytes, out_w, out_h, factor, dst_ptr, dst_bytes,
+                                          stream or None))
 
     # graphics.rs:59-61
     def update_parameters_buffer(self, parameters):
@@ -202,7 +231,7 @@ class Renderer:
     def pixel_keys(self):
         """The 8-bit cost keys (16 log2(bodies + 1)) the last persistent launch recorded per
         local pixel, row-major (scheduling diagnostics)."""
-        n = self.width * self.height
+        n = self.render_width * self.render_height
         out = np.zeros(n, np.uint8)
         got = self._lib.frm_debug_pixel_keys(self.ctx, out.ctypes.data, n)
         if got < 0:
@@ -217,7 +246,7 @@ class Renderer:
     def trace(self):
         """frm_debug_trace: the shading inputs of every pixel of the last render, (H, W, 10) float32
         in the oracle's trace layout (hit, steps, normal xyz, sun hit, sun closeness, colour xyz)."""
-        out = np.zeros((self.height, self.width, 10), np.float32)
+        out = np.zeros((self.render_height, self.render_width, 10), np.float32)
         self._check(self._lib.frm_debug_trace(self.ctx, out.ctypes.data, out.size))
         return out
 

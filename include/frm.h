@@ -192,6 +192,38 @@ int frm_device_count(int32_t* out_count);
  *      does not stall the frames already submitted. */
 int frm_resize(frm_ctx* ctx, uint32_t width, uint32_t height);
 
+/* ---- supersampled anti-aliasing (the offline counterpart of the reference's `>`/`<`
+ *      render-texture factor, render_texture_config.rs:1-22: render larger than shown). With a
+ *      factor S > 1 every frm_render renders the (S*width) x (S*height) frame, whose pixel centres
+ *      are exactly the S x S sub-sample centres of the width x height frame (aspect_scale stays the
+ *      caller's, from width and height), and resolves it on the same stream: each output channel is
+ *      the box mean of its S*S texels in linear light, as a filtering sampler over the
+ *      Rgba8UnormSrgb render texture averages them: decoded (the blit's table), added in f32 row
+ *      by row, left to right, divided by S*S (correctly rounded) and stored as the sRGB store
+ *      does; alpha 255. frm_resize takes the OUTPUT size (factor x width and height at most
+ *      FRM_MAX_DIMENSION); frm_read_frame, frm_present, their async forms and frm_frame_pixels see
+ *      the resolved frame at that size. frm_stats counts the rendered frame (pixels = S*S x width
+ *      x height) and kernel_ms includes the resolve; frm_debug_trace and frm_debug_*pixel_keys stay
+ *      at the render size. Factor 1 (the default) allocates nothing and changes no path.
+ * frm_set_supersampling: factor 1..FRM_MAX_SUPERSAMPLE (FRM_ERR_INVALID_ARGUMENT otherwise, or when
+ *      the current size times the factor exceeds FRM_MAX_DIMENSION; the old factor stays). With a
+ *      size set, a change acts as frm_resize of the current output size: no drain, frames in flight
+ *      and their tickets keep their bytes and shapes, async readbacks give FRM_ERR_NOT_READY until
+ *      the next frm_render. A group context applies it to every member. On a supersampled context
+ *      frm_render_bands, frm_render_bands_batch and frm_unshuffle_bands are FRM_ERR_UNSUPPORTED
+ *      (render the bands at S x the size on a plain context, then frm_resolve).
+ * frm_resolve: the resolve alone, on any context, asynchronous on `stream`: dev_src holds
+ *      factor*out_height rows of factor*out_width RGBA8 sRGB texels (pitch 4*factor*out_width),
+ *      dev_dst out_height rows of out_width, both device memory of the context's GPU (devices[0]
+ *      of a group), 4-byte aligned, not overlapping (FRM_ERR_INVALID_ARGUMENT otherwise;
+ *      FRM_ERR_BUFFER_TOO_SMALL when src_bytes or dst_bytes is short). The source alpha is
+ *      ignored; factor 1 copies the texels with alpha 255. */
+#define FRM_MAX_SUPERSAMPLE 4u
+int frm_set_supersampling(frm_ctx* ctx, uint32_t factor);
+int frm_get_supersampling(const frm_ctx* ctx, uint32_t* out_factor);
+int frm_resolve(frm_ctx* ctx, const uint8_t* dev_src, size_t src_bytes, uint32_t out_width,
+                uint32_t out_height, uint32_t factor, uint8_t* dev_dst, size_t dst_bytes, void* stream);
+
 /* ---- uniform upload (replaces Graphics::update_parameters_buffer,
  *      graphics.rs:59-61 → queue.write_buffer, persistent_graphics.rs:167-173).
  *      The struct is copied; it reaches the kernel by value. FRM_ERR_UNSUPPORTED (the previous
