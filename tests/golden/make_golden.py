@@ -4,8 +4,10 @@
 The reference (Rust + WGSL) cannot be built or executed here and ships no fixtures or
 golden images, so these vectors are produced by the CPU oracle (oracle/frm_oracle.c,
 MODE_FRM) and pin it against regressions; its correctness is established separately by
-closed-form known answers (tests/test_oracle_kat.py), the float64-libm cross-check
-(tests/test_p1_semantic.py) and the independent host compile of the product source
+closed-form known answers (tests/test_oracle_kat.py), the independent float64 numpy
+restatement of the shader (tests/f64_reference.py, held against the oracle by
+tests/test_f64_reference.py), the float64-libm cross-check (tests/test_p1_semantic.py, same
+structure, other builtins) and the independent host compile of the product source
 (tests/test_host_replay.py). Contents:
   frames.json  — sha256 of the RGBA8 bytes + the 8 work counters of 64x36 frames for all
                  19 scenes x num_iterations {0,3,6} x time {0, 3.2175055} (pose P1,
