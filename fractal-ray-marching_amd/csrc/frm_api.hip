@@ -1484,6 +1484,33 @@ int frm_resolve(frm_ctx* ctx, const uint8_t* dev_src, size_t src_bytes, uint32_t
   return FRM_OK;
 }
 
+int frm_blit(frm_ctx* ctx, const uint8_t* dev_src, size_t src_bytes, uint32_t src_width, uint32_t src_height,
+             uint8_t* dev_dst, size_t dst_bytes, uint32_t out_width, uint32_t out_height, uint32_t flags, void* stream) {
+  if (!ctx || !dev_src || !dev_dst) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "ctx/dev_src/dev_dst is NULL");
+  if (src_width == 0 || src_height == 0 || src_width > FRM_MAX_DIMENSION || src_height > FRM_MAX_DIMENSION)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "source size %ux%u outside [1, %u]^2", src_width, src_height,
+                FRM_MAX_DIMENSION);
+  if (out_width == 0 || out_height == 0 || out_width > FRM_MAX_DIMENSION || out_height > FRM_MAX_DIMENSION)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "output size %ux%u outside [1, %u]^2", out_width, out_height,
+                FRM_MAX_DIMENSION);
+  if (flags & ~(FRM_BLIT_SRGB | FRM_BLIT_BGRA)) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "unknown flags 0x%x", flags);
+  const uintptr_t sa = reinterpret_cast<uintptr_t>(dev_src), da = reinterpret_cast<uintptr_t>(dev_dst);
+  if (sa % 4u || da % 4u) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "dev_src / dev_dst not 4-byte aligned");
+  const size_t src_need = (size_t)src_width * src_height * 4u, dst_need = (size_t)out_width * out_height * 4u;
+  if (src_bytes < src_need)
+    return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "src holds %zu bytes, %ux%u texels need %zu", src_bytes, src_width,
+                src_height, src_need);
+  if (dst_bytes < dst_need)
+    return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "dst holds %zu bytes, the output needs %zu", dst_bytes, dst_need);
+  if (sa < da + dst_need && da < sa + src_need)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "dev_src and dev_dst overlap");
+  FRM_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = ring_leave(ctx)) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  FRM_HIP(ctx, launch_blit(dev_src, src_width, src_height, dev_dst, out_width, out_height, flags, s));
+  return FRM_OK;
+}
+
 int frm_set_parameters(frm_ctx* ctx, const frm_parameters* parameters) {
   if (!ctx || !parameters) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "ctx/parameters is NULL");
   SceneUniforms su;

@@ -127,6 +127,9 @@ SIGNATURES = [
     ("frm_reload", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
     ("frm_present", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]),
+    ("frm_blit", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,
+      ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]),
     ("frm_read_frame_async", ctypes.c_int, [ctypes.c_void_p, _P(ctypes.c_uint64)]),
     ("frm_present_async", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _P(ctypes.c_uint64)]),

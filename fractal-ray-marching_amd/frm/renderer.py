@@ -113,6 +113,14 @@ class Renderer:
         self._check(self._lib.frm_present(self.ctx, width, height, flags, buf.ctypes.data, buf.nbytes))
         return buf
 
+    def blit(self, src_ptr, src_bytes, src_w, src_h, dst_ptr, dst_bytes, out_w, out_h, srgb=True, bgra=False,
+             stream=0):
+        """frm_blit: present()'s resample of src_h x src_w RGBA8 sRGB texels at device pointer src_ptr
+        into out_h x out_w at dst_ptr, asynchronously on `stream` (0: the context's)."""
+        flags = (_lib.FRM_BLIT_SRGB if srgb else 0) | (_lib.FRM_BLIT_BGRA if bgra else 0)
+        self._check(self._lib.frm_blit(self.ctx, src_ptr, src_bytes, src_w, src_h, dst_ptr, dst_bytes, out_w, out_h,
+                                       flags, stream or None))
+
     # asynchronous readback (frm_read_frame_async / frm_present_async + frm_frame_pixels): the
     # reference's surface presents with a frame of latency (wgpu's desired_maximum_frame_latency
     # 2), so a loop renders frame k, starts its readback and then waits for frame k-1's pixels

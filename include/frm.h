@@ -253,6 +253,16 @@ int frm_read_frame(frm_ctx* ctx, uint8_t* dst, size_t dst_bytes);
 #define FRM_BLIT_BGRA 0x2u
 int frm_present(frm_ctx* ctx, uint32_t out_width, uint32_t out_height, uint32_t flags, uint8_t* dst,
                 size_t dst_bytes);
+/* frm_blit: that blit alone, on any context, asynchronous on `stream` (NULL: the context's):
+ * dev_src holds src_height rows of src_width RGBA8 sRGB texels (pitch 4*src_width), dev_dst
+ * receives out_height rows of out_width, both device memory of the context's GPU (devices[0]
+ * of a group), 4-byte aligned, not overlapping, every size in [1, FRM_MAX_DIMENSION]
+ * (FRM_ERR_INVALID_ARGUMENT otherwise, or for unknown flags; FRM_ERR_BUFFER_TOO_SMALL when
+ * src_bytes or dst_bytes is short). The source alpha is ignored, the output alpha is 255.
+ * frm_present(w, h, flags) is frm_blit of frm_read_frame's bytes. */
+int frm_blit(frm_ctx* ctx, const uint8_t* dev_src, size_t src_bytes, uint32_t src_width, uint32_t src_height,
+             uint8_t* dev_dst, size_t dst_bytes, uint32_t out_width, uint32_t out_height, uint32_t flags,
+             void* stream);
 int frm_synchronize(frm_ctx* ctx);
 
 /* ---- asynchronous readback: presentation with a frame of latency, as the reference's

@@ -9,7 +9,8 @@ from helpers import params_for
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("out_w,out_h", [(160, 90), (400, 225), (80, 45), (320, 90), (97, 61), (1, 1)])
+@pytest.mark.parametrize("out_w,out_h", [(160, 90), (400, 225), (80, 45), (320, 90), (97, 61), (1, 1),
+                                         (320, 45), (53, 200)])  # one axis magnified, the other minified
 @pytest.mark.parametrize("flags", [1, 0, 2, 3])
 def test_present_matches_oracle(gpu_renderer_factory, oracle, out_w, out_h, flags):
     p = params_for(18, 6, 3.2175055, 160, 90)
