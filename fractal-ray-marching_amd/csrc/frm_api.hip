@@ -93,6 +93,7 @@ struct Slot {
   bool sched_history = false;
   uint32_t sched_w = 0, sched_h = 0;  // frame size of the recorded keys when they cover a whole frame
   bool sched_whole = false;
+  uint32_t sched_npix = 0;  // local pixels of the slot's last persistent launch (<= sched_cap)
   // another slot's launch copied this slot's keys as its scheduling history (on keys_reader):
   // this slot's next launch, which rewrites them, waits for that copy
   hipEvent_t keys_read = nullptr;
@@ -590,6 +591,7 @@ int launch(frm_ctx* ctx, KernelArgs a, hipStream_t s, uint32_t* out_slot = nullp
     sl.sched_whole = whole;
     sl.sched_w = a.f.width;
     sl.sched_h = a.f.height;
+    sl.sched_npix = npix;
     unsigned int* dbg = sl.queue + kQueueDebugWord;
     a.debug = (unsigned long long*)dbg;  // the diagnostic words after the partition counters
 #ifdef FRM_STAMPS
@@ -1920,19 +1922,42 @@ extern "C" int frm_debug_read(frm_ctx* ctx, uint64_t* out5) {
 }
 #endif
 
-// per-pixel cost keys recorded by the last persistent launch (local pixel order; before
-// the next launch overwrites them)
-int frm_debug_pixel_keys(frm_ctx* ctx, uint8_t* out, size_t n) {
-  if (!ctx || !out) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (ctx->group) return not_on_group(ctx, "frm_debug_pixel_keys");
+// The scheduling state in the slot of the last persistent launch, copied out for
+// frm_debug_pixel_keys (keys) and frm_debug_pixel_order (order, ranked): min(n, that launch's
+// local pixels) entries, the count in *copied. Returns a frm_status.
+static int debug_sched_read(frm_ctx* ctx, const char* what, uint8_t* keys, uint32_t* order, uint32_t* ranked, size_t n,
+                            size_t* copied) {
+  if (ctx->group) return not_on_group(ctx, what);
   if (int rc = ring_leave(ctx)) return rc;
   const Slot& sl = ctx->slots[(ctx->next_slot + ctx->nslots - 1u) % ctx->nslots];  // last launch
-  if (!sl.sched_keys) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "no persistent launch yet");
-  if (n > sl.sched_cap) n = sl.sched_cap;
+  if (!sl.sched_keys || !sl.sched_order || !sl.sched_npix)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "%s: no persistent launch yet", what);
+  if (n > sl.sched_npix) n = sl.sched_npix;
   FRM_HIP(ctx, hipSetDevice(ctx->device));
   FRM_HIP(ctx, hipDeviceSynchronize());
-  FRM_HIP(ctx, hipMemcpy(out, sl.sched_keys, n, hipMemcpyDeviceToHost));
-  return (int)n;
+  if (keys) FRM_HIP(ctx, hipMemcpy(keys, sl.sched_keys, n, hipMemcpyDeviceToHost));
+  if (order) FRM_HIP(ctx, hipMemcpy(order, sl.sched_order, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (ranked) *ranked = sl.order_ready ? 1u : 0u;
+  *copied = n;
+  return FRM_OK;
+}
+
+// per-pixel cost keys recorded by the last persistent launch (local pixel order; before
+// the next launch overwrites them); the count copied, or a negative frm_status
+int frm_debug_pixel_keys(frm_ctx* ctx, uint8_t* out, size_t n) {
+  if (!ctx || !out) return -fail(ctx, FRM_ERR_INVALID_ARGUMENT, "NULL argument");
+  size_t copied = 0;
+  const int rc = debug_sched_read(ctx, "frm_debug_pixel_keys", out, nullptr, nullptr, n, &copied);
+  return rc ? -rc : (int)copied;
+}
+
+// the fetch order in the last persistent launch's slot: the one that launch ranked for the slot's
+// next launch of the same geometry (*out_ranked = 1), else the one it fetched by itself (0)
+int frm_debug_pixel_order(frm_ctx* ctx, uint32_t* out, size_t n, uint32_t* out_ranked) {
+  if (!ctx || !out || !out_ranked) return -fail(ctx, FRM_ERR_INVALID_ARGUMENT, "NULL argument");
+  size_t copied = 0;
+  const int rc = debug_sched_read(ctx, "frm_debug_pixel_order", nullptr, out, out_ranked, n, &copied);
+  return rc ? -rc : (int)copied;
 }
 
 // replaces the cost keys the next launch sorts its pixels by (scheduling experiments): the

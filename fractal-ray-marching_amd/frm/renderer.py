@@ -243,13 +243,26 @@ class Renderer:
         out = np.zeros(n, np.uint8)
         got = self._lib.frm_debug_pixel_keys(self.ctx, out.ctypes.data, n)
         if got < 0:
-            self._check(got)
+            self._check(-got)
         return out[:got]
 
     def set_pixel_keys(self, keys):
         """Replace the cost keys the next persistent launch sorts its pixels by."""
         k = np.ascontiguousarray(keys, dtype=np.uint8)
         self._check(self._lib.frm_debug_set_pixel_keys(self.ctx, k.ctypes.data, k.size))
+
+    def pixel_order(self, n=None):
+        """frm_debug_pixel_order: (order, ranked). The fetch order in the last persistent launch's
+        slot (local pixel indices, most expensive first); ranked: that launch ranked it from its own
+        keys for the slot's next launch, else it is the order the launch itself fetched by.
+        n: the capacity offered (default: a whole frame at the render size)."""
+        n = self.render_width * self.render_height if n is None else int(n)
+        out = np.zeros(max(n, 1), np.uint32)
+        ranked = ctypes.c_uint32()
+        got = self._lib.frm_debug_pixel_order(self.ctx, out.ctypes.data, n, ctypes.byref(ranked))
+        if got < 0:
+            self._check(-got)
+        return out[:got], int(ranked.value)
 
     def trace(self):
         """frm_debug_trace: the shading inputs of every pixel of the last render, (H, W, 10) float32

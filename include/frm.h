@@ -144,7 +144,7 @@ typedef struct frm_config {
                          reassembles the frame there; frm_read_frame, frm_present and their async
                          forms then see the whole frame, exactly as on one GPU. The per-rank band
                          entry points (frm_render_bands*, frm_unshuffle_bands, frm_debug_trace,
-                         frm_debug_*_pixel_keys) are FRM_ERR_UNSUPPORTED on a group. No reference
+                         frm_debug_*pixel_keys, frm_debug_pixel_order) are FRM_ERR_UNSUPPORTED on a group. No reference
                          counterpart (the reference is single-device, graphics.rs:25-37).       */
   int32_t devices[16];  /* HIP device ordinals of a group (FRM_MAX_DEVICES)                        */
 } frm_config;
@@ -203,8 +203,8 @@ int frm_resize(frm_ctx* ctx, uint32_t width, uint32_t height);
  *      does; alpha 255. frm_resize takes the OUTPUT size (factor x width and height at most
  *      FRM_MAX_DIMENSION); frm_read_frame, frm_present, their async forms and frm_frame_pixels see
  *      the resolved frame at that size. frm_stats counts the rendered frame (pixels = S*S x width
- *      x height) and kernel_ms includes the resolve; frm_debug_trace and frm_debug_*pixel_keys stay
- *      at the render size. Factor 1 (the default) allocates nothing and changes no path.
+ *      x height) and kernel_ms includes the resolve; frm_debug_trace, frm_debug_*pixel_keys and
+ *      frm_debug_pixel_order stay at the render size. Factor 1 (the default) allocates nothing and changes no path.
  * frm_set_supersampling: factor 1..FRM_MAX_SUPERSAMPLE (FRM_ERR_INVALID_ARGUMENT otherwise, or when
  *      the current size times the factor exceeds FRM_MAX_DIMENSION; the old factor stays). With a
  *      size set, a change acts as frm_resize of the current output size: no drain, frames in flight
@@ -381,6 +381,16 @@ int frm_debug_pixel_keys(frm_ctx* ctx, uint8_t* out, size_t n);
 /* frm_debug_set_pixel_keys: replaces the keys the next persistent launch orders its pixels by
  * (n = width x height; the next slot must hold a whole frame of the current size). */
 int frm_debug_set_pixel_keys(frm_ctx* ctx, const uint8_t* keys, size_t n);
+/* frm_debug_pixel_order: the fetch order held by the slot of the context's last persistent launch:
+ * a permutation of that launch's local pixels 0..pixels-1, most expensive key first; copies
+ * min(n, pixels) entries and returns that count, or a negative frm_status (as frm_debug_pixel_keys:
+ * the device is synchronised first, FRM_ERR_UNSUPPORTED on a group, FRM_ERR_INVALID_ARGUMENT before
+ * any persistent launch). *out_ranked = 1: that launch ranked its own keys into the order, which
+ * the slot's next launch of the same geometry fetches by (the default); 0: the buffer still holds
+ * the order that launch itself fetched by (FRM_SCHED=sort, runtime-reloaded kernels): a stable
+ * descending sort of the keys it started from, or 0..pixels-1 without history. Equal keys are in
+ * pixel order only when out_ranked is 0. Additive: FRM_ABI_VERSION stays 5. */
+int frm_debug_pixel_order(frm_ctx* ctx, uint32_t* out, size_t n, uint32_t* out_ranked);
 
 /* frm_debug_trace: the geometric inputs of the shading of every pixel of the last frm_render (a
  * whole frame on the persistent kernel, with the size and parameters that render used; refused

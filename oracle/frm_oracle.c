@@ -281,6 +281,7 @@ static int is_finite(float v) { return fabsf(v) < INFINITY; }
 
 typedef struct {
   uint64_t primary, shadow, normal, hits, pixels, bodies, bailouts;
+  uint64_t cost; /* scheduling cost (om_render_costs): Mandelbulb loop bodies run, else DE evaluations */
   om_census* census; /* NULL unless a census was asked for; per thread like the counters */
 } om_counts;
 
@@ -533,6 +534,7 @@ static float mandelbulb(const om_frame* F, vec3 position, om_counts* C) {
     b_sincos(m, phi * power, &sp, &cp);
     current = vmadd(exp_magnitude, V(st * cp, sp * st, ct), position);
     C->bodies++;
+    C->cost++; /* a DE that bails out at entry adds 0, a count exit N + 1 */
   }
   const float de = ((0.5f * b_log(m, magnitude)) * magnitude) / magnitude_derivative;
   census_mb_distance(C, magnitude, magnitude_derivative, de);
@@ -542,13 +544,14 @@ static float mandelbulb(const om_frame* F, vec3 position, om_counts* C) {
 static float scene(const om_frame* F, vec3 p, vec3* color, om_counts* C) {
   float d;
   switch (F->family) {
-    case 1: d = sierpinski(F, p); census_de(C, d); if (color) *color = colorize(vscale(p, 1.5f)); return d;
+    case 1: d = sierpinski(F, p); census_de(C, d); C->cost++; if (color) *color = colorize(vscale(p, 1.5f)); return d;
     case 2: d = koch(F, p); break;
     case 3: d = mandelbulb(F, p, C); break;
     case 4: d = vlength(p) - 0.5f; break;
     default: d = menger_sponge(F, p); break;
   }
   if (F->family != 3) census_de(C, d);
+  if (F->family != 3) C->cost++;
   if (color) *color = colorize(p);
   return d;
 }
@@ -716,6 +719,7 @@ typedef struct {
   float* linear;
   uint32_t* info;
   float* trace;
+  uint32_t* cost;
   uint32_t next; /* atomic row cursor (rayon-like dynamic schedule) */
   pthread_mutex_t mu;
   om_counts total;
@@ -737,6 +741,7 @@ static void* worker(void* arg) {
     for (uint32_t x = 0; x < W; ++x) {
       uint32_t inf;
       const size_t i = (size_t)r * W + x;
+      const uint64_t cost0 = C.cost;
       vec3 c = fragment(J->F, x, y, &C, &inf, J->trace ? J->trace + OM_TRACE_FLOATS * i : NULL);
       C.pixels++;
       uint8_t* px = J->rgba + 4 * i;
@@ -750,6 +755,7 @@ static void* worker(void* arg) {
         J->linear[3 * i + 2] = c.z;
       }
       if (J->info) J->info[i] = inf;
+      if (J->cost) J->cost[i] = (uint32_t)(C.cost - cost0);
     }
   }
   pthread_mutex_lock(&J->mu);
@@ -787,7 +793,7 @@ static void frame_from_params(om_frame* F, const uint8_t* params96, uint32_t wid
 static int render_impl(const uint8_t* params96, uint32_t width, uint32_t height, uint32_t max_steps,
                        uint32_t flags, int mode, const uint32_t* rows, uint32_t nrows, int threads,
                        uint8_t* out_rgba, uint64_t* counters, float* out_linear, uint32_t* out_info,
-                       float* out_trace, om_census* census) {
+                       float* out_trace, om_census* census, uint32_t* out_cost) {
   if (!params96 || !out_rgba || width == 0 || height == 0 || threads < 1) return 1;
   for (uint32_t i = 0; rows && i < nrows; ++i)
     if (rows[i] >= height) return 1;
@@ -804,6 +810,7 @@ static int render_impl(const uint8_t* params96, uint32_t width, uint32_t height,
   J.info = out_info;
   J.trace = out_trace;
   J.census = census;
+  J.cost = out_cost;
   pthread_mutex_init(&J.mu, NULL);
   pthread_t* tid = (pthread_t*)calloc((size_t)threads, sizeof(pthread_t));
   if (!tid) return 2;
@@ -833,7 +840,22 @@ int om_render_trace(const uint8_t* params96, uint32_t width, uint32_t height, ui
                     uint8_t* out_rgba, uint64_t* counters, float* out_linear, uint32_t* out_info,
                     float* out_trace) {
   return render_impl(params96, width, height, max_steps, flags, mode, rows, nrows, threads, out_rgba, counters,
-                     out_linear, out_info, out_trace, NULL);
+                     out_linear, out_info, out_trace, NULL, NULL);
+}
+
+/* The scheduling cost of every pixel of the rendered rows (out[nrows x width]): what libfrm's
+ * 8-bit cost keys are defined on (frm_render_kernels.h pix_cost). Mandelbulb: the loop bodies run
+ * over all of the pixel's DEs (primary march, four normal taps, shadow march); every other family
+ * and the sphere: its DE evaluations. Counted as the march runs, step 0 included, per pixel. */
+int om_render_costs(const uint8_t* params96, uint32_t width, uint32_t height, uint32_t max_steps,
+                    uint32_t flags, int mode, const uint32_t* rows, uint32_t nrows, int threads, uint32_t* out) {
+  if (!out || width == 0 || nrows == 0) return 1;
+  uint8_t* rgba = (uint8_t*)malloc((size_t)nrows * width * 4u);
+  if (!rgba) return 2;
+  int rc = render_impl(params96, width, height, max_steps, flags, mode, rows, nrows, threads, rgba, NULL, NULL, NULL,
+                       NULL, NULL, out);
+  free(rgba);
+  return rc;
 }
 
 /* The census layout, so that a binding can check its name tables against it. */
@@ -858,7 +880,7 @@ int om_render_census(const uint8_t* params96, uint32_t width, uint32_t height, u
   om_census K;
   census_init(&K);
   int rc = render_impl(params96, width, height, max_steps, flags, mode, rows, nrows, threads, out_rgba, counters,
-                       out_linear, out_info, out_trace, &K);
+                       out_linear, out_info, out_trace, &K, NULL);
   if (rc == 0) census_out(&K, out_census_n, out_census_x);
   return rc;
 }

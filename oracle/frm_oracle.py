@@ -61,6 +61,8 @@ def load():
         lib.om_render.restype = ctypes.c_int
         lib.om_render_trace.argtypes = lib.om_render.argtypes + [f32p]
         lib.om_render_trace.restype = ctypes.c_int
+        lib.om_render_costs.argtypes = lib.om_render.argtypes[:9] + [u32p]
+        lib.om_render_costs.restype = ctypes.c_int
         lib.om_shade_trace.argtypes = [u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                        ctypes.c_int, u32p, ctypes.c_uint32, f32p, u8p]
         lib.om_shade_trace.restype = ctypes.c_int
@@ -135,6 +137,25 @@ def render(params, width, height, max_steps, flags=0, mode=MODE_FRM, rows=None, 
         out["trace"] = tr
     if census:
         out["census"] = _census_dict(cn, cx)
+    return out
+
+
+def render_costs(params, width, height, max_steps, flags=0, mode=MODE_FRM, rows=None, threads=None):
+    """The scheduling cost of every pixel of the rows (default all) -> [n, W] uint32: Mandelbulb
+    loop bodies over all of the pixel's DEs, DE evaluations for every other family and the sphere
+    (om_render_costs; what libfrm's cost keys are 16 log2(cost + 1) of)."""
+    lib = load()
+    pb = _params_buf(params)
+    if rows is None:
+        nrows, rows_arr, rows_ptr = height, None, None
+    else:
+        rows_arr = np.ascontiguousarray(rows, dtype=np.uint32)
+        nrows, rows_ptr = len(rows_arr), rows_arr.ctypes.data
+    out = np.zeros((nrows, width), dtype=np.uint32)
+    rc = lib.om_render_costs(pb.ctypes.data, width, height, max_steps, flags, mode, rows_ptr, nrows,
+                             threads or os.cpu_count() or 1, out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"om_render_costs failed ({rc})")
     return out
 
 

@@ -25,6 +25,8 @@ int om_render_census(const uint8_t* params96, uint32_t width, uint32_t height, u
                      uint64_t* out_census_n, float* out_census_x);
 int om_scene_de_census(const uint8_t* params96, uint32_t flags, int mode, const float* pts, uint32_t n, float* out_d,
                        float* out_color, uint64_t* out_counts, uint64_t* out_census_n, float* out_census_x);
+int om_render_costs(const uint8_t* params96, uint32_t width, uint32_t height, uint32_t max_steps, uint32_t flags,
+                    int mode, const uint32_t* rows, uint32_t nrows, int threads, uint32_t* out);
 void om_census_layout(uint32_t* counts, uint32_t* extremes, uint32_t* maxima);
 int om_math(int fn, int mode, const float* a, const float* b, uint32_t n, float* out);
 int om_blit(const uint8_t* src, uint32_t sw, uint32_t sh, uint8_t* dst, uint32_t dw, uint32_t dh, uint32_t flags);
@@ -97,6 +99,10 @@ int main(int argc, char** argv) {
         if (om_render_census((const uint8_t*)&q, w, h, 32, 0, 0, nullptr, h, threads, rgba.data(), c, nullptr, nullptr,
                              nullptr, cen_n.data(), cen_x.data()))
           return fail("om_render_census");
+        // the per-pixel scheduling costs of the two rows: exactly 2 x w entries
+        std::vector<uint32_t> costs((size_t)2 * w);
+        if (om_render_costs((const uint8_t*)&q, w, h, 32, 0, 0, rows, 2, threads, costs.data()))
+          return fail("om_render_costs");
       }
     }
   }
