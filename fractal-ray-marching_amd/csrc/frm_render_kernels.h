@@ -688,6 +688,9 @@ template <uint32_t FAM, bool ITERS, bool MULTI = false, bool ANIM = false, bool 
 #ifndef FRM_RING_WAVES_PER_SIMD
 #define FRM_RING_WAVES_PER_SIMD FRM_MARCH_WAVES_PER_SIMD
 #endif
+#ifndef FRM_LEAN_PASS
+#define FRM_LEAN_PASS 1  // 0: every service pass takes the full path (A/B builds)
+#endif
 __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MARCH_WAVES_PER_SIMD) void march_persistent(
     KernelArgs a) {
   __shared__ float4 chunk_rays[kMarchWaves][kChunk];  // per wave: camera ray xyz + record index bits
@@ -711,6 +714,9 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
   const SceneUniforms& su = a.s;
   constexpr bool kMb = is_mandelbulb(FAM);     // resumable body loop
   constexpr bool kHw = FAM == kMandelbulbHw;   // FRM_FLAG_HW_MATH
+  // The lean service pass (below): the Mandelbulb launches (single, MULTI, ANIM, hardware math).
+  // Not the ring grid (its register budget is fragile), nor the fixed-trip families.
+  constexpr bool kLeanPass = FRM_LEAN_PASS && kMb && !RES;
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
   const uint64_t lane_bit = 1ull << lane;
   constexpr bool multi = MULTI;
@@ -766,7 +772,7 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
                           // its scheduling key; the wave's body total is counted in SGPRs
 #ifdef FRM_STAMPS
   uint64_t stamp_service = 0, n_service = 0, n_loop = 0, real_exhaust = 0;
-  uint64_t stamp_consume = 0, stamp_refill = 0, n_fetch = 0;
+  uint64_t stamp_consume = 0, stamp_refill = 0, n_fetch = 0, n_lean = 0;
   uint64_t stamp_sub[4] = {0, 0, 0, 0};  // consume: distance, primary, taps, shadow
   const uint64_t stamp_begin = __builtin_amdgcn_s_memtime();
   const uint64_t stamp_real0 = __builtin_amdgcn_s_memrealtime();
@@ -781,6 +787,7 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
     // Body phase (Mandelbulb): one loop body per computing lane per iteration, until
     // a.service_min lanes wait for a service pass (finished DE, or idle with work left)
     // or no lane computes. The service pass costs the same however many lanes take part.
+    [[maybe_unused]] uint64_t live_m = 0, cons_m = 0;  // kLeanPass: live lanes, consuming lanes (SGPRs)
     if constexpr (kMb) {
       // The loop keeps its lane sets as wave-uniform masks (SGPRs): `pending` predicates the
       // body directly (inverse ballot -> exec) and one ballot per iteration retires lanes,
@@ -816,6 +823,8 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
         pending &= ~(ballot(body > n_iter) | ballot(mag > su.mb_bailout));
       }
       done = !lane_in(pending);  // idle lanes: masked by cons
+      live_m = live;
+      cons_m = live & ~pending;
     }
 
     // Service pass.
@@ -851,10 +860,49 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
         FRM_SUB_END(0);
       }
     }
-    const bool ev_prim = cons && phase == kPrimary, ev_shadow = cons && phase == kShadow;
+    // Lean pass (wave-uniform): no live lane is in a tap or shadow phase and no consuming lane
+    // hits in this pass, so every consuming lane is a primary ray that marches on or ends as a
+    // miss. That holds from a wave's start until its first hit and again once the hit pixels of
+    // the longest-first order have drained: the primary rays of miss pixels run under two bodies
+    // per DE, so those waves need a pass after about every body iteration. A pass in which a
+    // lane hits takes the full path below (de is computed, nothing is redone).
+    bool lean = false;
+    [[maybe_unused]] uint64_t prim_m = 0, hit_m = 0;  // consuming primary lanes; lanes with a hit distance
+    if constexpr (kLeanPass) {  // (the body loop's masks: one compare per term, combined in SGPRs)
+      const uint64_t other_m = ballot(phase != kPrimary);
+      hit_m = ballot(de <= kMinDistance);
+      prim_m = cons_m & ~other_m;
+      lean = ((live_m & other_m) | (cons_m & hit_m)) == 0;
+    }
+    bool need_point = false;
+    bool ev_prim = false, ev_hit = false, ev_shadow = false;  // what the full path's lanes consumed
+    if (lean) {
+      // the full path's primary miss step without the shadow closeness, the tap sums and the
+      // phase updates no lane here can need; the same t, it and record bits
+      if (cons) {
+        t += de;
+        it++;
+        need_point = it < f.max_steps && t < kMaxTotalDistance;
+        if (!need_point) {  // primary miss (flags 0: BACKGROUND_COLOR)
+          const uint2 tail = make_uint2(__float_as_uint(closeness), psteps | (cost_key(pix_cost) << kRecKeyShift));
+          *reinterpret_cast<uint2*>(&tails[pix]) = tail;
+          pix = kIdle;
+        }
+      }
+      n_prim += (uint64_t)__popcll(cons_m);
+#ifdef FRM_STAMPS
+      n_lean++;
+#endif
+    } else {
+    if constexpr (kLeanPass) {  // work counters, from the masks while they are at hand
+      n_prim += (uint64_t)__popcll(prim_m);
+      n_hit += (uint64_t)__popcll(prim_m & hit_m);
+      n_shadow += (uint64_t)__popcll(cons_m & ballot(phase == kShadow));
+    }
+    ev_prim = cons && phase == kPrimary, ev_shadow = cons && phase == kShadow;
     const bool tap = cons && !ev_prim && !ev_shadow;  // normal taps k.xyy, k.yyx, k.yxy, k.xxx
     const bool hit = de <= kMinDistance;              // object_result.distance >= 0
-    const bool ev_hit = ev_prim && hit;
+    ev_hit = ev_prim && hit;
     // shadow closeness = min(closeness, d / t) before t moves (d / 0 on step 0, as in
     // fragment.wgsl:292); computed by every lane, kept by shadow lanes
     const float cl = min_(closeness, de / t);
@@ -868,7 +916,7 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
     psteps = ev_hit ? it : psteps;
     const bool fin = (step && !more) || (ev_shadow && hit);  // primary miss, or shadow march ends
     const bool sun_miss = ev_shadow && step && !more;
-    bool need_point = ev_hit || (step && more) || tap;  // start a DE at the phase's next sample point
+    need_point = ev_hit || (step && more) || tap;  // start a DE at the phase's next sample point
     // tap k adds s_k * d to the sum (k = 0 sets it); s_0..s_3 = (+--), (--+), (-+-), (+++)
     const uint32_t k = phase - kTap0;
     const float dx = (k == 0u || k == 3u) ? de : -de, dy = (k >= 2u) ? de : -de,
@@ -912,6 +960,8 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
       pix = kIdle;
       FRM_SUB_END(3);
     }
+    }  // !lean
+    if constexpr (kLeanPass) n_bail += count(ev_bail);
     if constexpr (RES) {  // drained slots whose last pixels left the lanes
       const uint32_t gone = rw_get(rw, kRwGone);
       if (gone) ring_settle(ring_lds, rw, gone, pix);
@@ -992,7 +1042,13 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
             const uint32_t lp =
                 RES ? dev_load(&rl_ptr(((const volatile RingLds*)ring_lds)->order)[r_slot * a.rec_stride + pos0 + lane])
                     : a.pixel_order[pos0 + lane];
-            const uint32_t lr = lp / f.width, x = lp - lr * f.width, y = band_row_to_global(a.g, lr);
+            // (lean-pass kernels: the two divisors as this block's own values, so that the
+            // divisions' reciprocals are worked out here, once per chunk, instead of living in
+            // VGPRs across the whole march loop, where one of them spilled)
+            uint32_t fw = f.width;
+            BandGeometry bg = a.g;
+            if constexpr (kLeanPass) asm volatile("" : "+s"(fw), "+s"(bg.band_rows));
+            const uint32_t lr = lp / fw, x = lp - lr * fw, y = band_row_to_global(bg, lr);
             if constexpr (RES)
               ray = camera_ray_rows(f, row, x, y);
             else if constexpr (multi)
@@ -1052,12 +1108,21 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
     //    taps is recomputed from the unchanged primary ray: ray_at(o, t_hit, d))
     if (need_point) {
       const v3 r = ray_at(o, t, d);
-      // normal tap k samples r + s_k * MIN_DISTANCE (normal_tap_pos), with selects
-      const uint32_t kq = phase - kTap0;
-      const bool is_tap = kq <= kTap3 - kTap0;
-      const float e = kMinDistance;
-      const float ex = (kq == 0u || kq == 3u) ? e : -e, ey = (kq >= 2u) ? e : -e, ez = (kq == 1u || kq == 3u) ? e : -e;
-      q = mk(is_tap ? r.x + ex : r.x, is_tap ? r.y + ey : r.y, is_tap ? r.z + ez : r.z);
+      // no tap among the lanes that start a DE (every lean pass: a refill only adds primary
+      // lanes): the point itself. Tested here again: the lean flag carried across the refill is a
+      // lane mask that the register allocator parks in two VGPR lanes, four lane moves per pass.
+      bool no_tap = false;
+      if constexpr (kLeanPass) no_tap = ballot(phase - kTap0 <= kTap3 - kTap0) == 0;
+      if (no_tap) {
+        q = r;
+      } else {
+        // normal tap k samples r + s_k * MIN_DISTANCE (normal_tap_pos), with selects
+        const uint32_t kq = phase - kTap0;
+        const bool is_tap = kq <= kTap3 - kTap0;
+        const float e = kMinDistance;
+        const float ex = (kq == 0u || kq == 3u) ? e : -e, ey = (kq >= 2u) ? e : -e, ez = (kq == 1u || kq == 3u) ? e : -e;
+        q = mk(is_tap ? r.x + ex : r.x, is_tap ? r.y + ey : r.y, is_tap ? r.z + ez : r.z);
+      }
       if constexpr (kMb) {
         z = q;
         dr = 1.f;
@@ -1074,7 +1139,7 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
 
     // work counters (frm_stats); a ring grid's frames report none (frm_render with stats renders
     // outside the ring), so it keeps no counters
-    if constexpr (!RES) {
+    if constexpr (!RES && !kLeanPass) {
       n_prim += count(ev_prim);
       n_hit += count(ev_hit);
       n_shadow += count(ev_shadow);
@@ -1111,6 +1176,7 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
       r[9] = stamp_refill;
       r[10] = n_fetch;
       for (int k = 0; k < 4; ++k) r[11 + k] = stamp_sub[k];
+      r[15] = n_lean;  // service passes that took the lean path
       r[0] = n_loop;
       r[1] = n_body;
       r[2] = n_service;

@@ -54,6 +54,9 @@ print(f"service pass cycles: consume {cons.sum() / nserv.sum():.0f}, refill {ref
       f"fetches per wave {nfetch.mean():.1f}")
 sub = [rec[:, 11 + k].astype(np.float64).sum() / nserv.sum() for k in range(4)]
 print("sub-stamps, cycles per pass: [0] %.0f, [1] %.0f, [2] %.0f, [3] %.0f" % tuple(sub))
+nlean = rec[:, 15].astype(np.float64)
+print(f"lean passes {nlean.sum():.0f} of {nserv.sum():.0f} service passes: share {nlean.sum() / nserv.sum():.3f}; "
+      f"waves with a lean share above one half {(nlean > 0.5 * nserv).mean():.3f}")
 print(f"wave start spread {st.max():.0f} us; first exhaust {np.nanmin(ex):.0f} us, median exhaust {np.nanmedian(ex):.0f} us")
 q = np.percentile(en, [0, 10, 50, 90, 99, 100])
 print("wave end percentiles (us): " + " ".join(f"p{p_}={v:.0f}" for p_, v in zip([0, 10, 50, 90, 99, 100], q)))
