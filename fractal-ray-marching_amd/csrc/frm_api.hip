@@ -79,6 +79,14 @@ struct Slot {
   // presentation paths read; alternating with the framebuffers, so fb_read[i] covers its readers too
   uint8_t* res[2] = {nullptr, nullptr};
   size_t res_cap[2] = {0, 0};
+  // adaptive supersampling (frm_set_adaptive, factor > 1): res[i] holds the adaptive frame of fbs[i]
+  // (adaptive[i]: the slot's last frm_render into fbs[i] was adaptive), and the slot's scratch of
+  // the pass: the list of refined pixels (refine_cap entries) and its control words
+  bool adaptive[2] = {false, false};
+  uint32_t* refine_list = nullptr;
+  size_t refine_cap = 0;
+  uint32_t* refine_ctl = nullptr;
+  uint32_t refine_w = 0, refine_h = 0;  // the frame the list belongs to
   unsigned int* queue = nullptr;
   uint8_t* records = nullptr;  // persistent kernel scratch (ShadeGeom[cap] then ShadeTail[cap]), grown on demand
   size_t records_cap = 0;
@@ -216,6 +224,8 @@ struct frm_ctx {
   uint32_t width = 0, height = 0;  // the internal render size: supersample x the output size
   uint32_t supersample = 1;        // frm_set_supersampling
   uint32_t out_width = 0, out_height = 0;  // frm_resize's size: what the presentation paths show
+  uint32_t adaptive = 1;                   // frm_set_adaptive: samples per axis of a refined pixel (1: off)
+  uint32_t edge_threshold = FRM_ADAPTIVE_DEFAULT_THRESHOLD;
   Slot slots[FRM_MAX_FRAMES_IN_FLIGHT];
   uint32_t nslots = 1;
   uint32_t next_slot = 0;  // slot of the next launch
@@ -338,20 +348,54 @@ int ensure_res(frm_ctx* ctx, Slot& sl, size_t bytes) {
   sl.res_cap[i] = bytes;
   return FRM_OK;
 }
-// The frame of the slot's current framebuffer at the output size, on the slot stream, after the
-// frame is complete there: the box resolve of a supersampled context. The slot's `done` event is
-// recorded again, so that it covers the resolved image.
+// The scratch of the slot's adaptive pass for a frame of npix pixels, grown on the slot stream (the
+// slot's last pass ran there).
+int ensure_refine(frm_ctx* ctx, Slot& sl, size_t npix) {
+  int rc = FRM_OK;
+  if (!sl.refine_ctl && (rc = dev_alloc(ctx, (void**)&sl.refine_ctl, kRefineCtlBytes, sl.stream))) return rc;
+  if (sl.refine_cap >= npix) return FRM_OK;
+  if ((rc = dev_release(ctx, sl.refine_list, sl.stream))) return rc;
+  sl.refine_list = nullptr;
+  sl.refine_cap = 0;
+  if ((rc = dev_alloc(ctx, (void**)&sl.refine_list, npix * sizeof(uint32_t), sl.stream))) return rc;
+  sl.refine_cap = npix;
+  return FRM_OK;
+}
+// The second image of the slot's current framebuffer, on the slot stream, after the frame is
+// complete there: the box resolve of a supersampled context, or the adaptive frame of an adaptive
+// one (the edge pass over the frame, then the samples of its refined pixels; their work is added
+// to the context's counters). The slot's `done` event is recorded again, so that it covers it.
 int resolve_frame(frm_ctx* ctx, Slot& sl) {
-  if (ctx->supersample == 1u) return FRM_OK;
+  sl.adaptive[sl.fb_idx] = false;
+  if (ctx->supersample == 1u && ctx->adaptive == 1u) return FRM_OK;
   const size_t bytes = (size_t)ctx->out_width * ctx->out_height * 4u;
   if (int rc = ensure_res(ctx, sl, bytes + bytes / 4u)) return rc;
-  FRM_HIP(ctx, launch_resolve(sl.fb, sl.res[sl.fb_idx], ctx->out_width, ctx->out_height, ctx->supersample, sl.stream));
+  if (ctx->adaptive > 1u) {  // (excludes supersampling: the render size is the output size)
+    if (int rc = ensure_refine(ctx, sl, (size_t)ctx->width * ctx->height)) return rc;
+    FrameUniforms f;
+    compute_frame_uniforms(ctx->params, ctx->adaptive * ctx->width, ctx->adaptive * ctx->height, ctx->max_steps, &f);
+    FRM_HIP(ctx, launch_adaptive(f, ctx->scene, sl.fb, sl.res[sl.fb_idx], ctx->width, ctx->height, ctx->adaptive,
+                                 ctx->edge_threshold, sl.refine_list, sl.refine_ctl, ctx->counters, ctx->cu_count,
+                                 sl.stream));
+    sl.adaptive[sl.fb_idx] = true;
+    sl.refine_w = ctx->width;
+    sl.refine_h = ctx->height;
+  } else {
+    FRM_HIP(ctx, launch_resolve(sl.fb, sl.res[sl.fb_idx], ctx->out_width, ctx->out_height, ctx->supersample, sl.stream));
+  }
   FRM_HIP(ctx, hipEventRecord(sl.done, sl.stream));
   return FRM_OK;
 }
 // What the presentation paths read of a slot: out_width x out_height texels.
 const uint8_t* shown(const frm_ctx* ctx, const Slot& sl) {
-  return ctx->supersample > 1u ? sl.res[sl.fb_idx] : sl.fb;
+  return ctx->supersample > 1u || sl.adaptive[sl.fb_idx] ? sl.res[sl.fb_idx] : sl.fb;
+}
+
+int not_adaptive(frm_ctx* ctx, const char* what) {
+  return fail(ctx, FRM_ERR_UNSUPPORTED,
+              "%s: not available on an adaptive context (frm_set_adaptive); render the bands on a plain "
+              "context and call frm_refine",
+              what);
 }
 
 uint32_t num_bands(uint32_t height, uint32_t band_rows) { return (height + band_rows - 1) / band_rows; }
@@ -793,7 +837,7 @@ uint32_t ring_size(const frm_ctx* ctx) { return ctx->nslots >= 3 ? 4u : 2u; }
 // Whether frm_render(ctx, NULL) goes through the ring.
 bool ring_eligible(const frm_ctx* ctx) {
   if (!ctx->ring_enabled || ctx->group || ctx->bands_only || ctx->reloaded || ctx->nslots < 2) return false;
-  if (ctx->supersample > 1u) return false;  // ring frames are not resolved
+  if (ctx->supersample > 1u || ctx->adaptive > 1u) return false;  // ring frames are not resolved or refined
   const uint64_t npix = (uint64_t)ctx->width * ctx->height;
   if (kernel_for(ctx, npix) != kKernelPersistent || npix > (1ull << 28)) return false;
   // a ring's service waves give up after kRingWatchdogTicks (2 s) without progress: keep the
@@ -1029,6 +1073,7 @@ int ring_materialize(frm_ctx* ctx) {
   const size_t bytes = (size_t)ctx->width * ctx->height * 4u;
   if ((rc = select_fb(ctx, sl, sl.fb_idx)) || (rc = ensure_fb(ctx, sl, bytes + bytes / 4u))) return rc;
   const uint32_t s = (R.last_seq - 1u) & (R.slots - 1u);
+  sl.adaptive[sl.fb_idx] = false;
   FRM_HIP(ctx, hipMemcpyAsync(sl.fb, R.out + (size_t)s * R.w * R.h, bytes, hipMemcpyDeviceToDevice, ctx->stream));
   FRM_HIP(ctx, hipEventRecord(sl.done, ctx->stream));
   sl.pending = true;
@@ -1346,7 +1391,7 @@ int frm_destroy(frm_ctx* ctx) {
     Slot& sl = ctx->slots[i];
     // pool blocks back to the pool (every stream is idle), then the pool itself below
     if (ctx->stream)
-      for (void* b : {(void*)sl.fbs[0], (void*)sl.fbs[1], (void*)sl.res[0], (void*)sl.res[1], (void*)sl.records, (void*)sl.sched_iota, (void*)sl.sched_order,
+      for (void* b : {(void*)sl.fbs[0], (void*)sl.fbs[1], (void*)sl.res[0], (void*)sl.res[1], (void*)sl.refine_list, (void*)sl.refine_ctl, (void*)sl.records, (void*)sl.sched_iota, (void*)sl.sched_order,
                       (void*)sl.sched_keys, sl.sched_temp, (void*)sl.present_dev})
         if (b) (void)hipFreeAsync(b, ctx->stream);
     if (sl.queue) (void)hipFree(sl.queue);
@@ -1401,6 +1446,7 @@ static int resize_render(frm_ctx* ctx, uint32_t width, uint32_t height) {
   ctx->width = width;
   ctx->height = height;
   ctx->last_slot = 0;
+  for (Slot& sl : ctx->slots) sl.adaptive[0] = sl.adaptive[1] = false;  // adaptive frames of the old size
   // no frame of the new size yet: frm_read_frame_async / frm_present_async refuse until the next
   // frm_render (tickets issued before keep their frames)
   ctx->render_seq = 0;
@@ -1427,10 +1473,12 @@ static int apply_size(frm_ctx* ctx, uint32_t width, uint32_t height, uint32_t fa
 
 int frm_resize(frm_ctx* ctx, uint32_t width, uint32_t height) {
   if (!ctx) return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  const uint32_t limit = FRM_MAX_DIMENSION / ctx->supersample;
+  // an adaptive frame's refined pixels are those of its full supersampled counterpart: the same bound
+  const uint32_t factor = ctx->adaptive > 1u ? ctx->adaptive : ctx->supersample;
+  const uint32_t limit = FRM_MAX_DIMENSION / factor;
   if (width == 0 || height == 0 || width > limit || height > limit)
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "frame size %ux%u outside [1, %u]^2 (supersampling %u)", width, height,
-                limit, ctx->supersample);
+                limit, factor);
   return apply_size(ctx, width, height, ctx->supersample);
 }
 
@@ -1439,6 +1487,11 @@ int frm_set_supersampling(frm_ctx* ctx, uint32_t factor) {
   if (factor == 0 || factor > FRM_MAX_SUPERSAMPLE)
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "supersampling factor %u outside [1, %u]; factor not changed", factor,
                 FRM_MAX_SUPERSAMPLE);
+  if (factor > 1u && ctx->adaptive > 1u)
+    return fail(ctx, FRM_ERR_UNSUPPORTED,
+                "supersampling factor %u on an adaptive context (frm_set_adaptive): switch that off first; "
+                "factor not changed",
+                factor);
   if (ctx->out_width) {
     const uint32_t limit = FRM_MAX_DIMENSION / factor;
     if (ctx->out_width > limit || ctx->out_height > limit)
@@ -1484,6 +1537,129 @@ int frm_resolve(frm_ctx* ctx, const uint8_t* dev_src, size_t src_bytes, uint32_t
   hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
   FRM_HIP(ctx, launch_resolve(dev_src, dev_dst, out_width, out_height, factor, s));
   return FRM_OK;
+}
+
+int frm_set_adaptive(frm_ctx* ctx, uint32_t factor, uint32_t threshold) {
+  if (!ctx) return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (factor == 0 || factor > FRM_MAX_SUPERSAMPLE || threshold > 256u)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT,
+                "adaptive factor %u outside [1, %u] or edge threshold %u above 256; values not changed", factor,
+                FRM_MAX_SUPERSAMPLE, threshold);
+  const uint32_t limit = FRM_MAX_DIMENSION / factor;
+  if (ctx->out_width > limit || ctx->out_height > limit)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT,
+                "adaptive factor %u: the %ux%u frame's samples would lie on a frame above %u texels a side; values "
+                "not changed",
+                factor, ctx->out_width, ctx->out_height, FRM_MAX_DIMENSION);
+  if (factor > 1u && ctx->supersample > 1u)
+    return fail(ctx, FRM_ERR_UNSUPPORTED,
+                "adaptive factor %u on a supersampled context (frm_set_supersampling): switch that off first; values "
+                "not changed",
+                factor);
+  if (factor > 1u && ctx->reloaded)
+    return fail(ctx, FRM_ERR_UNSUPPORTED,
+                "adaptive factor %u with runtime-reloaded kernels (frm_reload): the refine kernel is built in; values "
+                "not changed",
+                factor);
+  if (factor == ctx->adaptive && threshold == ctx->edge_threshold) return FRM_OK;
+  // No drain: frames in flight and their tickets keep their bytes; like a size change, there is no
+  // frame under the new setting for the async readbacks until the next frm_render.
+  if (ctx->width) {
+    FRM_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = ring_leave(ctx)) return rc;
+  }
+  ctx->adaptive = factor;
+  ctx->edge_threshold = threshold;
+  ctx->render_seq = 0;
+  return FRM_OK;
+}
+
+int frm_get_adaptive(const frm_ctx* ctx, uint32_t* out_factor, uint32_t* out_threshold) {
+  if (!ctx || !out_factor || !out_threshold)
+    return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "ctx/out_factor/out_threshold is NULL");
+  *out_factor = ctx->adaptive;
+  *out_threshold = ctx->edge_threshold;
+  return FRM_OK;
+}
+
+int frm_refine(frm_ctx* ctx, const frm_parameters* params, const uint8_t* dev_src, size_t src_bytes, uint32_t width,
+               uint32_t height, uint32_t factor, uint32_t threshold, uint8_t* dev_dst, size_t dst_bytes,
+               uint64_t* dev_counters, void* stream) {
+  if (!ctx || !dev_src || !dev_dst) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "ctx/dev_src/dev_dst is NULL");
+  if (factor == 0 || factor > FRM_MAX_SUPERSAMPLE || threshold > 256u)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "adaptive factor %u outside [1, %u] or edge threshold %u above 256", factor,
+                FRM_MAX_SUPERSAMPLE, threshold);
+  const uint32_t limit = FRM_MAX_DIMENSION / factor;
+  if (width == 0 || height == 0 || width > limit || height > limit)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "frame size %ux%u outside [1, %u]^2 (factor %u)", width, height, limit,
+                factor);
+  const uintptr_t sa = reinterpret_cast<uintptr_t>(dev_src), da = reinterpret_cast<uintptr_t>(dev_dst);
+  if (sa % 4u || da % 4u) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "dev_src / dev_dst not 4-byte aligned");
+  if (reinterpret_cast<uintptr_t>(dev_counters) % 8u)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "dev_counters not 8-byte aligned");
+  const size_t need = (size_t)width * height * 4u;
+  if (src_bytes < need)
+    return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "src holds %zu bytes, %ux%u texels need %zu", src_bytes, width, height, need);
+  if (dst_bytes < need)
+    return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "dst holds %zu bytes, the frame needs %zu", dst_bytes, need);
+  if (sa < da + need && da < sa + need) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "dev_src and dev_dst overlap");
+  frm_parameters p;
+  SceneUniforms su;
+  if (params) {
+    p = *params;
+    compute_scene_uniforms(p, ctx->flags, &su);
+    if (int rc = check_parameters(ctx, su, p)) return rc;
+  } else {
+    if (!ctx->has_params) return fail(ctx, FRM_ERR_NOT_READY, "params is NULL and frm_set_parameters has not been called");
+    p = ctx->params;
+    su = ctx->scene;
+  }
+  FRM_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = ring_leave(ctx)) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  // scratch per call, allocated and released in the order of the call's stream: calls in flight on
+  // different streams never share it
+  uint32_t *list = nullptr, *ctl = nullptr;
+  int rc = dev_alloc(ctx, (void**)&list, need, s);
+  if (rc) return rc;
+  if ((rc = dev_alloc(ctx, (void**)&ctl, kRefineCtlBytes, s))) {
+    (void)hipFreeAsync(list, s);
+    return rc;
+  }
+  FrameUniforms f;
+  compute_frame_uniforms(p, factor * width, factor * height, ctx->max_steps, &f);
+  const hipError_t e = launch_adaptive(f, su, dev_src, dev_dst, width, height, factor, threshold, list, ctl,
+                                       (unsigned long long*)dev_counters, ctx->cu_count, s);
+  const int r1 = dev_release(ctx, list, s), r2 = dev_release(ctx, ctl, s);
+  if (e != hipSuccess) return hip_fail(ctx, e, "launch_adaptive");
+  return r1 ? r1 : r2;
+}
+
+int frm_debug_refine_mask(frm_ctx* ctx, uint8_t* out, size_t n) {
+  if (!ctx || !out) return -fail(ctx, FRM_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (ctx->last_is_ring || !ctx->render_seq)
+    return -fail(ctx, FRM_ERR_NOT_READY, "frm_debug_refine_mask: no adaptive frm_render under the current settings");
+  const Slot& sl = ctx->slots[ctx->last_slot];
+  if (!sl.adaptive[sl.fb_idx] || sl.seq != ctx->render_seq || !sl.refine_list)
+    return -fail(ctx, FRM_ERR_NOT_READY, "frm_debug_refine_mask: the last frm_render was not adaptive");
+  const size_t npix = (size_t)sl.refine_w * sl.refine_h;
+  if (n > npix) n = npix;
+  if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(sl.stream) != hipSuccess)
+    return -fail(ctx, FRM_ERR_HIP, "frm_debug_refine_mask: synchronisation failed");
+  uint32_t count = 0;
+  if (hipMemcpy(&count, sl.refine_ctl, sizeof(count), hipMemcpyDeviceToHost) != hipSuccess || count > npix)
+    return -fail(ctx, FRM_ERR_HIP, "frm_debug_refine_mask: reading the list length failed");
+  uint32_t* list = new (std::nothrow) uint32_t[count ? count : 1u];
+  if (!list) return -fail(ctx, FRM_ERR_OUT_OF_MEMORY, "host allocation failed");
+  if (count && hipMemcpy(list, sl.refine_list, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) {
+    delete[] list;
+    return -fail(ctx, FRM_ERR_HIP, "frm_debug_refine_mask: reading the list failed");
+  }
+  memset(out, 0, n);
+  for (uint32_t k = 0; k < count; ++k)
+    if (list[k] < n) out[list[k]] = 1;
+  delete[] list;
+  return (int)n;
 }
 
 int frm_blit(frm_ctx* ctx, const uint8_t* dev_src, size_t src_bytes, uint32_t src_width, uint32_t src_height,
@@ -1732,6 +1908,8 @@ int frm_reload(frm_ctx* ctx, const char* source_dir) {
   // a group reloads every member: all compile, or every member keeps its kernels
   const uint32_t n = ctx->group ? ctx->group->n : 1u;
   ReloadedKernels* rk[FRM_MAX_DEVICES] = {};
+  if (source_dir && ctx->adaptive > 1u)  // the refine kernel is not part of the runtime-compiled source
+    return fail(ctx, FRM_ERR_UNSUPPORTED, "frm_reload on an adaptive context (frm_set_adaptive); previous kernels kept");
   if (source_dir)
     for (uint32_t r = 0; r < n; ++r) {
       std::string log;
@@ -1792,6 +1970,7 @@ int frm_render_bands(frm_ctx* ctx, uint8_t* dev_dst, size_t dst_bytes, uint32_t 
   if (rc) return rc;
   if (ctx->group) return not_on_group(ctx, "frm_render_bands");
   if (ctx->supersample > 1u) return not_supersampled(ctx, "frm_render_bands");
+  if (ctx->adaptive > 1u) return not_adaptive(ctx, "frm_render_bands");
   if (!dev_dst || band_rows == 0 || band_stride == 0)
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "invalid dst or band geometry");
   uint32_t rows = band_local_rows(ctx->height, band_rows, first_band, band_stride);
@@ -1813,6 +1992,7 @@ int frm_render_bands_batch(frm_ctx* ctx, uint32_t count, const frm_parameters* p
   if (!ctx) return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "ctx is NULL");
   if (ctx->group) return not_on_group(ctx, "frm_render_bands_batch");
   if (ctx->supersample > 1u) return not_supersampled(ctx, "frm_render_bands_batch");
+  if (ctx->adaptive > 1u) return not_adaptive(ctx, "frm_render_bands_batch");
   if (!ctx->width) return fail(ctx, FRM_ERR_NOT_READY, "frm_resize has not been called");
   if (!params || !dev_dst || count == 0 || count > FRM_MAX_BATCH || band_rows == 0 || band_stride == 0)
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "invalid batch (count %u, at most %u) or band geometry", count,
@@ -1899,6 +2079,7 @@ int frm_unshuffle_bands(frm_ctx* ctx, const uint8_t* dev_src, size_t rank_stride
   if (!ctx || !dev_src || !dev_dst || band_rows == 0 || ranks == 0)
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "invalid unshuffle arguments");
   if (ctx->supersample > 1u) return not_supersampled(ctx, "frm_unshuffle_bands");
+  if (ctx->adaptive > 1u) return not_adaptive(ctx, "frm_unshuffle_bands");
   if (!ctx->width) return fail(ctx, FRM_ERR_NOT_READY, "frm_resize has not been called");
   size_t need = (size_t)ctx->width * ctx->height * 4u;
   if (dst_bytes < need)

@@ -9,11 +9,16 @@
 //              [--simple] [--sphere] [--out file.ppm | pattern_%04d.ppm]
 //              [--frames F] [--dt S] [--keys BITS] [--orbit RAD_PER_S]
 //              [--lock-yaw 0..4] [--lock-pitch] [--time-factor X] [--gpus N] [--batch B]
-//              [--ssaa K]
+//              [--ssaa K] [--adaptive S] [--edge-threshold T]
 // With --ssaa K (1..4) every frame is rendered with K x K samples per pixel and resolved in linear
 // light (frm_set_supersampling); W x H stay the size of the written frames, the work counters in
 // the JSON lines are those of the (K*W) x (K*H) frame rendered. With --batch the context stays plain
 // at that size and each frame goes through frm_resolve before it is copied to the host.
+// With --adaptive S (1..4) every frame is rendered plainly and the pixels whose 3 x 3 neighbourhood has a
+// contrast of at least T sRGB codes (--edge-threshold, 0..256, default FRM_ADAPTIVE_DEFAULT_THRESHOLD)
+// are replaced by the resolve of their S x S samples (frm_set_adaptive); the JSON lines count the
+// plain frame plus the refined samples and give the number of refined pixels. With --batch each
+// frame goes through frm_refine with its own parameters. Not together with --ssaa.
 // With --batch B (one context) the fly-through's frames are rendered B per launch
 // (frm_render_bands_batch: one work queue for B frames whose camera and, for the Mandelbulb,
 // time differ), so a launch's tail is paid once per B frames; the frames' bytes are the same.
@@ -68,7 +73,7 @@ static int write_ppm(const char* out, uint32_t fr, const uint8_t* rgba, uint32_t
 // the launch's, reported per launch.
 static int render_batched(frm_ctx* ctx, frm_parameters p, frm_camera cam, frm_timing timing, uint32_t keys,
                           float dt, uint32_t frames, uint32_t batch, uint32_t width, uint32_t height,
-                          uint32_t ssaa, const char* out) {
+                          uint32_t ssaa, uint32_t adaptive, uint32_t edge_threshold, const char* out) {
   std::vector<frm_parameters> ps(frames);
   std::vector<frm_camera> cams(frames);
   for (uint32_t fr = 0; fr < frames; ++fr) {
@@ -86,34 +91,44 @@ static int render_batched(frm_ctx* ctx, frm_parameters p, frm_camera cam, frm_ti
   uint8_t *dev = nullptr, *resolved = nullptr;
   uint64_t* dcnt = nullptr;
   hip_check(hipMalloc(&dev, fb * batch), "hipMalloc");
-  if (ssaa > 1) hip_check(hipMalloc(&resolved, ofb * batch), "hipMalloc");
-  hip_check(hipMalloc(&dcnt, FRM_NUM_COUNTERS * sizeof(uint64_t)), "hipMalloc");
+  if (ssaa > 1 || adaptive > 1) hip_check(hipMalloc(&resolved, ofb * batch), "hipMalloc");
+  // the launch's counters, then one set per frame for its refined samples (--adaptive)
+  hip_check(hipMalloc(&dcnt, (1 + (size_t)batch) * FRM_NUM_COUNTERS * sizeof(uint64_t)), "hipMalloc");
+  std::vector<uint64_t> rc((size_t)batch * FRM_NUM_COUNTERS);
   std::vector<uint8_t> host(ofb * batch);
   char name[4096];
   for (uint32_t g = 0; g < frames; g += batch) {
     const uint32_t n = frames - g < batch ? frames - g : batch;
-    hip_check(hipMemset(dcnt, 0, FRM_NUM_COUNTERS * sizeof(uint64_t)), "hipMemset");
+    hip_check(hipMemset(dcnt, 0, (1 + (size_t)batch) * FRM_NUM_COUNTERS * sizeof(uint64_t)), "hipMemset");
     const auto t0 = std::chrono::steady_clock::now();
     check(frm_render_bands_batch(ctx, n, &ps[g], dev, fb * n, fb, rh, 0, 1, nullptr, dcnt), ctx,
           "frm_render_bands_batch");
     for (uint32_t b = 0; b < n && ssaa > 1; ++b)  // on the context's stream, after the launch
       check(frm_resolve(ctx, dev + fb * b, fb, width, height, ssaa, resolved + ofb * b, ofb, nullptr), ctx,
             "frm_resolve");
+    for (uint32_t b = 0; b < n && adaptive > 1; ++b)  // each frame's samples follow its own parameters
+      check(frm_refine(ctx, &ps[g + b], dev + fb * b, fb, width, height, adaptive, edge_threshold, resolved + ofb * b,
+                       ofb, dcnt + (1 + b) * FRM_NUM_COUNTERS, nullptr),
+            ctx, "frm_refine");
     check(frm_synchronize(ctx), ctx, "frm_synchronize");
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     uint64_t c[FRM_NUM_COUNTERS];
     hip_check(hipMemcpy(c, dcnt, sizeof(c), hipMemcpyDeviceToHost), "hipMemcpy");
-    hip_check(hipMemcpy(host.data(), ssaa > 1 ? resolved : dev, ofb * n, hipMemcpyDeviceToHost), "hipMemcpy");
+    hip_check(hipMemcpy(rc.data(), dcnt + FRM_NUM_COUNTERS, rc.size() * sizeof(uint64_t), hipMemcpyDeviceToHost), "hipMemcpy");
+    for (uint32_t b = 0; b < n; ++b)  // the launch's work: its frames plus their refined samples
+      for (uint32_t k = 0; k < FRM_NUM_COUNTERS; ++k) c[k] += rc[(size_t)b * FRM_NUM_COUNTERS + k];
+    hip_check(hipMemcpy(host.data(), resolved ? resolved : dev, ofb * n, hipMemcpyDeviceToHost), "hipMemcpy");
     for (uint32_t b = 0; b < n; ++b) {
       const uint32_t fr = g + b;
       if (write_ppm(out, fr, &host[ofb * b], width, height, name, sizeof(name))) return 1;
       printf("{\"frame\": %u, \"out\": \"%s\", \"width\": %u, \"height\": %u, \"time\": %.6f, "
              "\"pos\": [%.5f, %.5f, %.5f], \"yaw\": %.5f, \"pitch\": %.5f, \"kernel_ms\": %.3f, "
              "\"batch\": %u, \"launch_march_steps\": %llu, \"launch_hit_pixels\": %llu, \"gsteps_per_s\": %.3f, "
-             "\"ssaa\": %u}\n",
+             "\"ssaa\": %u, \"adaptive\": %u, \"edge_threshold\": %u, \"refined_pixels\": %llu}\n",
              fr, name, width, height, ps[fr].time, cams[fr].position[0], cams[fr].position[1], cams[fr].position[2],
              cams[fr].yaw, cams[fr].pitch, ms / n, n, (unsigned long long)(c[2] + c[3]), (unsigned long long)c[1],
-             (double)(c[2] + c[3]) / (ms * 1e-3) / 1e9, ssaa);
+             (double)(c[2] + c[3]) / (ms * 1e-3) / 1e9, ssaa, adaptive, edge_threshold,
+             (unsigned long long)(rc[(size_t)b * FRM_NUM_COUNTERS] / (adaptive * adaptive)));
     }
   }
   (void)hipFree(dev);
@@ -135,6 +150,8 @@ int main(int argc, char** argv) {
   uint32_t gpus = 0;  // 0: one GPU (--device); >= 1: a group context over devices 0..gpus-1
   uint32_t batch = 1;  // frames per launch (one context)
   uint32_t ssaa = 1;   // samples per pixel and axis
+  uint32_t adaptive = 1, edge_threshold = FRM_ADAPTIVE_DEFAULT_THRESHOLD;  // --adaptive, --edge-threshold
+  bool ssaa_given = false, adaptive_given = false;
   for (int i = 1; i < argc; ++i) {
     const char* a = argv[i];
     auto next = [&](void) -> const char* {
@@ -172,8 +189,26 @@ int main(int argc, char** argv) {
         return 2;
       }
       ssaa = (uint32_t)k;
+      ssaa_given = true;
+    }
+    else if (!strcmp(a, "--adaptive") || !strcmp(a, "--edge-threshold")) {
+      const bool thr = a[2] == 'e';
+      const long hi = thr ? 256 : (long)FRM_MAX_SUPERSAMPLE, lo = thr ? 0 : 1;
+      const char* v = next();
+      char* end = nullptr;
+      const long k = strtol(v, &end, 10);
+      if (end == v || *end || k < lo || k > hi) {
+        fprintf(stderr, "frm_render: %s %s outside [%ld, %ld]\n", a, v, lo, hi);
+        return 2;
+      }
+      (thr ? edge_threshold : adaptive) = (uint32_t)k;
+      adaptive_given = true;
     }
     else { fprintf(stderr, "unknown argument %s\n", a); return 2; }
+  }
+  if (ssaa_given && adaptive_given) {
+    fprintf(stderr, "frm_render: --adaptive / --edge-threshold and --ssaa exclude each other\n");
+    return 2;
   }
   frm_ctx* ctx = nullptr;
   frm_config cfg = {device, max_steps, flags, 0, 0, {0}};
@@ -212,6 +247,7 @@ int main(int argc, char** argv) {
   } else {
     check(frm_set_supersampling(ctx, ssaa), ctx, "frm_set_supersampling");
     check(frm_resize(ctx, width, height), ctx, "frm_resize");
+    check(frm_set_adaptive(ctx, adaptive, edge_threshold), ctx, "frm_set_adaptive");
   }
   std::vector<uint8_t> rgba((size_t)width * height * 4);
   if (batch < 1 || batch > FRM_MAX_BATCH) {
@@ -222,7 +258,8 @@ int main(int argc, char** argv) {
     fprintf(stderr, "frm_render: --batch renders on one GPU (frm_render_bands_batch is a per-device entry point)\n");
     return 2;
   }
-  if (batch > 1) return render_batched(ctx, p, cam, timing, keys, dt, frames, batch, width, height, ssaa, out);
+  if (batch > 1) return render_batched(ctx, p, cam, timing, keys, dt, frames, batch, width, height, ssaa, adaptive,
+                                   edge_threshold, out);
   for (uint32_t fr = 0; fr < frames; ++fr) {
     if (fr > 0) {  // initialized_app.rs:43-48, with a fixed frame time
       const float delta = frm_timing_update(&timing, &p, dt);
@@ -244,10 +281,12 @@ int main(int argc, char** argv) {
     fclose(f);
     printf("{\"frame\": %u, \"out\": \"%s\", \"width\": %u, \"height\": %u, \"time\": %.6f, "
            "\"pos\": [%.5f, %.5f, %.5f], \"yaw\": %.5f, \"pitch\": %.5f, \"kernel_ms\": %.3f, "
-           "\"march_steps\": %llu, \"hit_pixels\": %llu, \"gsteps_per_s\": %.3f, \"ssaa\": %u}\n",
+           "\"march_steps\": %llu, \"hit_pixels\": %llu, \"gsteps_per_s\": %.3f, \"ssaa\": %u, "
+           "\"adaptive\": %u, \"edge_threshold\": %u, \"refined_pixels\": %llu}\n",
            fr, name, width, height, p.time, cam.position[0], cam.position[1], cam.position[2], cam.yaw,
            cam.pitch, st.kernel_ms, (unsigned long long)st.march_steps, (unsigned long long)st.hit_pixels,
-           st.march_steps / (st.kernel_ms * 1e-3) / 1e9, ssaa);
+           st.march_steps / (st.kernel_ms * 1e-3) / 1e9, ssaa, adaptive, edge_threshold,
+           (unsigned long long)(adaptive > 1 ? (st.pixels - (uint64_t)width * height) / (adaptive * adaptive) : 0));
   }
   frm_destroy(ctx);
   return 0;

@@ -245,6 +245,17 @@ hipError_t launch_unshuffle(const uint8_t* src, size_t rank_stride, uint8_t* dst
 // with alpha 255).
 hipError_t launch_resolve(const uint8_t* src, uint8_t* dst, uint32_t dw, uint32_t dh, uint32_t factor,
                           hipStream_t stream);
+// Adaptive supersampling (frm_set_adaptive, frm_refine; frm_refine_kernels.h): dst = src with alpha
+// 255 (height rows of width RGBA8 sRGB texels, both 4-byte aligned, not overlapping), except the
+// pixels whose 3 x 3 neighbourhood in src has a contrast >= threshold: those are the box resolve
+// of their factor x factor samples of the frame f (of factor * width x factor * height) and scene s.
+// list: width * height u32 of scratch (afterwards the refined pixels' indices), ctl: kRefineCtlBytes
+// (ctl[0] afterwards their number); counters: the refined samples' work is added, or nullptr.
+// factor 1..4 (1: the copy alone).
+constexpr size_t kRefineCtlBytes = 512;
+hipError_t launch_adaptive(const FrameUniforms& f, const SceneUniforms& s, const uint8_t* src, uint8_t* dst,
+                           uint32_t width, uint32_t height, uint32_t factor, uint32_t threshold, uint32_t* list,
+                           uint32_t* ctl, unsigned long long* counters, int cu_count, hipStream_t stream);
 // Pixel scheduling (frm_sched.hip). With history, order = the local pixels 0..npix-1
 // (iota) by descending key[p], the cost key the last launch recorded for pixel p (stable,
 // one 8-bit radix pass); without, order = iota (row-major).

@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "frm_render_kernels.h"
+#include "frm_refine_kernels.h"
 
 namespace frm {
 

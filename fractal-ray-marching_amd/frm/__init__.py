@@ -6,6 +6,7 @@ src/graphics.rs) over the C ABI of include/frm.h (libfrm.so, HIP kernels for gfx
 from ._lib import (FRM_DEFAULT_MAX_STEPS, FRM_FLAG_PERSISTENT_KERNEL, FRM_FLAG_SCENE_SPHERE, FRM_FLAG_SIMPLE_KERNEL,
                    FRM_FLAG_HW_MATH, FRM_FLAG_UNBOUNDED_ITERATIONS,
                    FRM_MAX_BATCH, FRM_MAX_FRAMES_IN_FLIGHT, FRM_MAX_NUM_ITERATIONS, FRM_MAX_SUPERSAMPLE, FRM_NUM_COUNTERS, FRM_NUM_SCENES,
+                   FRM_ADAPTIVE_DEFAULT_THRESHOLD,
                    FrmError, LIB_PATH,
                    load)
 from .parameters import Camera, HeldKeys, Parameters, Timing
@@ -18,5 +19,5 @@ __all__ = [
     "FRM_DEFAULT_MAX_STEPS", "FRM_FLAG_PERSISTENT_KERNEL", "FRM_FLAG_SCENE_SPHERE", "FRM_FLAG_SIMPLE_KERNEL",
     "FRM_FLAG_UNBOUNDED_ITERATIONS", "FRM_FLAG_HW_MATH",
     "FRM_MAX_BATCH", "FRM_MAX_FRAMES_IN_FLIGHT", "FRM_MAX_NUM_ITERATIONS", "FRM_MAX_SUPERSAMPLE", "FRM_NUM_COUNTERS",
-    "FRM_NUM_SCENES",
+    "FRM_NUM_SCENES", "FRM_ADAPTIVE_DEFAULT_THRESHOLD",
 ]

@@ -26,6 +26,7 @@ FRM_MAX_FRAMES_IN_FLIGHT = 8
 FRM_MAX_DEVICES = 16
 FRM_MAX_BATCH = 32
 FRM_MAX_SUPERSAMPLE = 4
+FRM_ADAPTIVE_DEFAULT_THRESHOLD = 16
 FRM_DEFAULT_MAX_STEPS = 5000
 FRM_MAX_STEPS_LIMIT = 4194303
 FRM_MAX_NUM_ITERATIONS = 65536
@@ -119,6 +120,12 @@ SIGNATURES = [
     ("frm_resolve", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
       ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    ("frm_set_adaptive", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]),
+    ("frm_get_adaptive", ctypes.c_int, [ctypes.c_void_p, _P(ctypes.c_uint32), _P(ctypes.c_uint32)]),
+    ("frm_refine", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,
+      ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    ("frm_debug_refine_mask", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
     ("frm_set_parameters", ctypes.c_int, [ctypes.c_void_p, _P(FrmParameters)]),
     ("frm_render", ctypes.c_int, [ctypes.c_void_p, _P(FrmStats)]),
     ("frm_read_frame", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),

@@ -11,8 +11,10 @@ from . import _lib
 
 
 class Renderer:
-    def __init__(self, device=0, max_steps=0, flags=0, frames_in_flight=1, devices=None, supersampling=1):
+    def __init__(self, device=0, max_steps=0, flags=0, frames_in_flight=1, devices=None, supersampling=1,
+                 adaptive=None):
         """supersampling: samples per pixel and axis (frm_set_supersampling; 1 = off).
+        adaptive: (S, threshold) or S: S x S samples for the pixels on an edge only (frm_set_adaptive).
         devices: a list of HIP device ordinals for a GROUP context (frm_config.device_count):
         every frame is row-tiled over them and gathered on devices[0] (RCCL, or device copies
         when a device repeats); the rest of the API is the same."""
@@ -34,12 +36,15 @@ class Renderer:
         self.frames_in_flight = max(1, frames_in_flight)
         self.width = self.height = 0
         self.supersampling = 1
-        if supersampling != 1:
-            try:
+        self._adaptive = (1, _lib.FRM_ADAPTIVE_DEFAULT_THRESHOLD)
+        try:
+            if supersampling != 1:
                 self.set_supersampling(supersampling)
-            except Exception:
-                self.close()
-                raise
+            if adaptive is not None:
+                self.set_adaptive(*(adaptive if isinstance(adaptive, (tuple, list)) else (adaptive,)))
+        except Exception:
+            self.close()
+            raise
 
     def close(self):
         if self.ctx:
@@ -86,6 +91,39 @@ class Renderer:
         src_ptr into out_h x out_w at dst_ptr, asynchronously on `stream` (0: the context's)."""
         self._check(self._lib.frm_resolve(self.ctx, src_ptr, src_bytes, out_w, out_h, factor, dst_ptr, dst_bytes,
                                           stream or None))
+
+    def set_adaptive(self, factor, threshold=_lib.FRM_ADAPTIVE_DEFAULT_THRESHOLD):
+        """frm_set_adaptive: from the next render on, the pixels whose 3 x 3 neighbourhood in the plain
+        frame has a contrast of `threshold` sRGB codes or more (0: all, 256: none) are replaced by the
+        box resolve of their factor x factor samples; factor 1 switches it off."""
+        self._check(self._lib.frm_set_adaptive(self.ctx, factor, threshold))
+        self._adaptive = (int(factor), int(threshold))
+
+    @property
+    def adaptive(self):
+        """(factor, threshold) of frm_set_adaptive; factor 1 = off."""
+        return self._adaptive
+
+    def refine(self, src_ptr, src_bytes, width, height, factor, threshold, dst_ptr, dst_bytes, params=None,
+               dev_counters=0, stream=0):
+        """frm_refine: the adaptive frame of the height x width RGBA8 sRGB frame at device pointer
+        src_ptr into dst_ptr, its refined pixels sampled with `params` (None: the context's),
+        asynchronously on `stream` (0: the context's); dev_counters: FRM_NUM_COUNTERS device words the
+        refined samples' work is added to."""
+        raw = None
+        if params is not None:
+            raw = ctypes.byref(params.raw if hasattr(params, "raw") else params)
+        self._check(self._lib.frm_refine(self.ctx, raw, src_ptr, src_bytes, width, height, factor, threshold,
+                                         dst_ptr, dst_bytes, dev_counters or None, stream or None))
+
+    def refine_mask(self):
+        """frm_debug_refine_mask: the edge mask of the last (adaptive) render, (height, width) uint8 0/1."""
+        out = np.zeros((self.height, self.width), np.uint8)
+        got = self._lib.frm_debug_refine_mask(self.ctx, out.ctypes.data, out.size)
+        if got < 0:
+            self._check(-got)
+        assert got == out.size, (got, out.size)
+        return out
 
     # graphics.rs:59-61
     def update_parameters_buffer(self, parameters):

@@ -224,6 +224,50 @@ int frm_get_supersampling(const frm_ctx* ctx, uint32_t* out_factor);
 int frm_resolve(frm_ctx* ctx, const uint8_t* dev_src, size_t src_bytes, uint32_t out_width,
                 uint32_t out_height, uint32_t factor, uint8_t* dev_dst, size_t dst_bytes, void* stream);
 
+/* ---- adaptive supersampling: the S x S samples of frm_set_supersampling(S), taken only where the
+ *      plain frame has contrast. With F1 the plain width x height frame (frm_render's bytes without
+ *      this) and FS the frame frm_set_supersampling(S) gives for the same size and parameters:
+ *      output pixel (X, Y) is REFINED iff, over the 3 x 3 window around it clipped to the frame,
+ *      max over R, G, B of (max - min of the 8-bit sRGB codes of F1) >= threshold (alpha ignored;
+ *      threshold 0 refines every pixel, 256 none). The adaptive frame is FS where refined and F1
+ *      elsewhere, alpha 255, bit for bit. The render size stays the output size; the frame is rendered
+ *      as without this, then an edge pass and a refine pass run on the same stream.
+ *      frm_read_frame, frm_present, their async forms and frm_frame_pixels see the adaptive frame.
+ *      frm_stats holds F1's counters plus those of every refined sample (pixels = width x height +
+ *      S*S x refined pixels); kernel_ms includes both passes. Known limit: a feature thinner than a
+ *      pixel that no pixel centre of F1 hits leaves no contrast there and is not found.
+ * frm_set_adaptive: factor 1 (the default) switches it off; factor in 1..FRM_MAX_SUPERSAMPLE and
+ *      threshold in 0..256, and factor x the current size at most FRM_MAX_DIMENSION (which frm_resize
+ *      checks on an adaptive context too), else FRM_ERR_INVALID_ARGUMENT and the old values stay.
+ *      FRM_ERR_UNSUPPORTED (old values stay) with factor > 1 on a supersampled context, as is
+ *      frm_set_supersampling(k > 1) on an adaptive one, and with runtime-reloaded kernels active, as
+ *      is frm_reload(dir) on an adaptive one (the refine kernel is built in). A change takes effect at
+ *      the next frm_render without a drain: frames in flight and their tickets keep their bytes, async
+ *      readbacks give FRM_ERR_NOT_READY until that frm_render. A group context runs the two passes on
+ *      devices[0] after the reassembly. On an adaptive context frm_render_bands,
+ *      frm_render_bands_batch and frm_unshuffle_bands are FRM_ERR_UNSUPPORTED (render the bands on a
+ *      plain context, then frm_refine), and frames never go through the resident ring.
+ * frm_refine: the two passes alone, on any context, asynchronous on `stream`: dev_src holds the
+ *      plain frame (height rows of width RGBA8 sRGB texels; it need not be a frame of that scene,
+ *      refined pixels never read it), dev_dst receives the adaptive one; both device memory of the
+ *      context's GPU, 4-byte aligned, not overlapping (FRM_ERR_INVALID_ARGUMENT otherwise;
+ *      FRM_ERR_BUFFER_TOO_SMALL when src_bytes or dst_bytes is short). The samples are those of
+ *      `params` (checked as frm_set_parameters checks them; NULL: the context's, FRM_ERR_NOT_READY
+ *      without any) with the context's max_steps and flags. factor 1 copies the texels with alpha
+ *      255. dev_counters: NULL, or FRM_NUM_COUNTERS device words to which the refined samples' work
+ *      is added. Calls in flight on different streams are independent.
+ * frm_debug_refine_mask: the edge mask of the last frm_render, if it was adaptive (FRM_ERR_NOT_READY
+ *      otherwise): out[i] = 1 where pixel i (row-major) was refined, else 0, for the first
+ *      min(n, width x height) pixels; returns that count, or a negative frm_status. Synchronises
+ *      the frame. Additive: FRM_ABI_VERSION stays 5. */
+#define FRM_ADAPTIVE_DEFAULT_THRESHOLD 16u   /* sRGB codes; a product default, not a measured optimum */
+int frm_set_adaptive(frm_ctx* ctx, uint32_t factor, uint32_t threshold);
+int frm_get_adaptive(const frm_ctx* ctx, uint32_t* out_factor, uint32_t* out_threshold);
+int frm_refine(frm_ctx* ctx, const frm_parameters* params, const uint8_t* dev_src, size_t src_bytes,
+               uint32_t width, uint32_t height, uint32_t factor, uint32_t threshold, uint8_t* dev_dst,
+               size_t dst_bytes, uint64_t* dev_counters, void* stream);
+int frm_debug_refine_mask(frm_ctx* ctx, uint8_t* out, size_t n);
+
 /* ---- uniform upload (replaces Graphics::update_parameters_buffer,
  *      graphics.rs:59-61 → queue.write_buffer, persistent_graphics.rs:167-173).
  *      The struct is copied; it reaches the kernel by value. FRM_ERR_UNSUPPORTED (the previous
