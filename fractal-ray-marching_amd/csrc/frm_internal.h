@@ -209,6 +209,10 @@ struct KernelArgs {
   // the counters once by the first wave
   unsigned long long first_counts[3];
   uint32_t anim;
+  // Debug (launch_render: FRM_DEBUG_COUNTER_START, unset = 0): every wave of march_persistent
+  // starts its work counters at this value and takes it off again, in 64 bits, when it flushes
+  // them, so a small frame crosses the carry out of the counters' low words. No result changes.
+  uint32_t counter_start;
   RingArgs ring;  // march_persistent<..., RES = true>: the resident frame ring
 };
 

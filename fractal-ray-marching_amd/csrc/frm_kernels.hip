@@ -161,6 +161,14 @@ static int blocks_override() {  // experiments: FRM_BLOCKS_PER_CU
   return v >= 1 && v <= 64 ? v : 0;
 }
 
+// Debug: FRM_DEBUG_COUNTER_START (a u32; decimal, or hex with 0x) is the value at which every wave
+// of the built-in persistent kernels starts its work counters (KernelArgs::counter_start). Read
+// at every launch, so a test can change it between launches of one process.
+static uint32_t counter_start_override() {
+  const char* env = getenv("FRM_DEBUG_COUNTER_START");
+  return env ? (uint32_t)strtoul(env, nullptr, 0) : 0u;
+}
+
 // A reloaded module's kernel (frm_reload.hip) takes the same KernelArgs by value.
 static hipError_t module_launch(hipFunction_t fn, dim3 grid, dim3 block, hipStream_t stream, const KernelArgs& args) {
   void* params[] = {const_cast<KernelArgs*>(&args)};
@@ -250,6 +258,7 @@ static hipError_t launch_persistent(const KernelArgs& args, int cu_count, hipStr
   KernelArgs m = args;  // + the frames' step 0
   constexpr bool kAnimKernel = is_mandelbulb(FAM) && ITERS;  // the ANIM instantiation exists
   first_steps<FAM, ITERS>(m, kAnimKernel && args.anim);
+  m.counter_start = counter_start_override();
   if constexpr (kAnimKernel) {
     if (args.anim) {
       hipLaunchKernelGGL((march_persistent<FAM, ITERS, true, true>), dim3(blocks), dim3(kMarchBlock), 0, stream, m);

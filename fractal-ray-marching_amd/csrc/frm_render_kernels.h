@@ -671,6 +671,62 @@ constexpr uint32_t kWaveDebugSlots = 16384u;
 __device__ unsigned long long g_wave_debug[16u * kWaveDebugSlots];
 #endif
 
+// SGPR diet of march_persistent (profiles/round9/sgpr). The defaults
+// are what measured faster on the headline; 0 everywhere is the earlier code.
+#ifndef FRM_COUNTERS32
+#define FRM_COUNTERS32 1  // 0: the work counters as 64-bit SGPR pairs (A/B builds)
+#endif
+#ifndef FRM_QUEUE_RELOAD
+#define FRM_QUEUE_RELOAD 1  // 1: the drained mask in 32 bits; 2: and the queue's sizes worked out at each fetch (slower)
+#endif
+#ifndef FRM_LEAN_CARRY
+#define FRM_LEAN_CARRY 0  // 1: the start-DE block takes the pass's lean decision, not its own tap test (slower)
+#endif
+#ifndef FRM_HOT_SGPRS
+#define FRM_HOT_SGPRS 0  // 1: max_steps and service_min pinned to SGPRs of their own (slower)
+#endif
+
+// One work counter of a wave, exactly 64 bits wide. The loops add to its low word, one SGPR; the
+// carry is a wave-uniform branch to a cold block that bumps the high word, which nothing else
+// reads before the final flush, so the register allocator may park it in a spill lane. (As
+// uint64_t the six counters held twelve SGPRs across both loops.) The loops pay s_add_u32,
+// s_cmp, s_cbranch for the earlier s_add_u32, s_addc_u32. The empty asms keep the sum scalar (as
+// one overflow-add it became a VALU add) and the cold block a block (folded into the add it is
+// the add-with-carry pair again).
+struct WaveCounter {
+#if FRM_COUNTERS32
+  uint32_t lo, hi;
+  __device__ __forceinline__ explicit WaveCounter(uint32_t start) : lo(start), hi(0u) {}
+  __device__ __forceinline__ void add(uint32_t n) {
+    lo += n;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+s"(lo));
+#endif
+    if (__builtin_expect(lo < n, 0)) {
+      hi++;
+#if defined(__HIP_DEVICE_COMPILE__)
+      asm volatile("" : "+s"(hi));
+#endif
+    }
+  }
+  __device__ __forceinline__ uint64_t value() const { return ((uint64_t)hi << 32) | lo; }
+#else
+  uint64_t v;
+  __device__ __forceinline__ explicit WaveCounter(uint32_t start) : v(start) {}
+  __device__ __forceinline__ void add(uint32_t n) { v += n; }
+  __device__ __forceinline__ uint64_t value() const { return v; }
+#endif
+};
+// The drained-partitions mask: bits 0..kQueueParts-1 and the head's bit kQueueParts.
+template <bool NARROW>
+struct DrainMask {
+  typedef uint64_t type;
+};
+template <>
+struct DrainMask<true> {
+  typedef uint32_t type;
+};
+
 // MULTI: a multi-frame launch (frm_render_bands_batch, a.batch > 1), a separate instantiation.
 // Queue chunk c (64 fetch positions) is chunk c / batch of frame c % batch: the frames'
 // pixels interleave chunk by chunk, each frame's longest first, and a chunk's frame (camera)
@@ -736,9 +792,31 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
   // and the partitions it has found drained
   const uint32_t nchunks = (total + kChunk - 1u) / kChunk;
   uint32_t part = queue_part();
-  uint64_t drained = 0;  // bit x: partition x drained; bit kQueueParts: the head
+  // (FRM_QUEUE_RELOAD 2: the sizes above are worked out again from the kernel arguments at each
+  // chunk fetch, about once per 94 passes, instead of holding three SGPRs across the march loop.
+  // Off: with them gone the allocator keeps the kernarg pointer in SGPRs and repeats argument
+  // loads where they are used, service_min's in every body iteration.)
+  constexpr bool kQueueReload = FRM_QUEUE_RELOAD >= 2 && !RES;
+  typedef typename DrainMask<FRM_QUEUE_RELOAD >= 1 && !RES && (kQueueParts < 32u)>::type drain_t;
+  drain_t drained = 0;  // bit x: partition x drained; bit kQueueParts: the head
   const uint32_t nhead = nchunks / kQueueHeadDiv;
-  uint64_t n_pix = 0, n_hit = 0, n_prim = 0, n_shadow = 0, n_body = 0, n_bail = 0;
+  // work counters (frm_stats), each from the launch's debug start value (0 but for
+  // FRM_DEBUG_COUNTER_START, the test of the carries), which the flush takes off again
+  const uint32_t count0 = RES ? 0u : a.counter_start;
+  WaveCounter n_pix(count0), n_hit(count0), n_prim(count0), n_shadow(count0), n_body(count0), n_bail(count0);
+  // FRM_HOT_SGPRS: the march's step limit and the body loop's lane threshold as values of the
+  // kernel's own (the empty asm) instead of kernel arguments, which the allocator parks in a
+  // spill lane (max_steps, read back in every pass) or loads again where they are used. Off:
+  // the body loop's schedule changes with it and the headline is slower.
+  constexpr bool kHotSgprs = FRM_HOT_SGPRS && !RES;
+  uint32_t hot_max_steps = 0, hot_service_min = 0;
+  if constexpr (kHotSgprs) {
+    hot_max_steps = f.max_steps;
+    hot_service_min = a.service_min;
+    asm volatile("" : "+s"(hot_max_steps), "+s"(hot_service_min));
+  }
+  const uint32_t& max_steps = kHotSgprs ? hot_max_steps : f.max_steps;
+  const uint32_t& service_min = kHotSgprs ? hot_service_min : a.service_min;
 #ifdef FRM_COUNT_EXACT
   uint64_t n_dbg_total = 0, n_dbg_exact = 0;
 #endif
@@ -798,10 +876,10 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
       // the queue still has pixels
       const uint64_t waitable = exhausted ? live : ~0ull;
       for (;;) {
-        if (pending == 0 || (uint32_t)__popcll(waitable & ~pending) >= a.service_min) break;
+        if (pending == 0 || (uint32_t)__popcll(waitable & ~pending) >= service_min) break;
         // one body per computing lane this iteration (a DE that bails out at entry never
         // becomes pending, so this counts bodies exactly: fragment.wgsl:245-249)
-        if constexpr (!RES) n_body += (uint64_t)__popcll(pending);
+        if constexpr (!RES) n_body.add((uint32_t)__popcll(pending));
 #ifdef FRM_STAMPS
         n_loop++;
 #endif
@@ -882,22 +960,22 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
       if (cons) {
         t += de;
         it++;
-        need_point = it < f.max_steps && t < kMaxTotalDistance;
+        need_point = it < max_steps && t < kMaxTotalDistance;
         if (!need_point) {  // primary miss (flags 0: BACKGROUND_COLOR)
           const uint2 tail = make_uint2(__float_as_uint(closeness), psteps | (cost_key(pix_cost) << kRecKeyShift));
           *reinterpret_cast<uint2*>(&tails[pix]) = tail;
           pix = kIdle;
         }
       }
-      n_prim += (uint64_t)__popcll(cons_m);
+      n_prim.add((uint32_t)__popcll(cons_m));
 #ifdef FRM_STAMPS
       n_lean++;
 #endif
     } else {
     if constexpr (kLeanPass) {  // work counters, from the masks while they are at hand
-      n_prim += (uint64_t)__popcll(prim_m);
-      n_hit += (uint64_t)__popcll(prim_m & hit_m);
-      n_shadow += (uint64_t)__popcll(cons_m & ballot(phase == kShadow));
+      n_prim.add((uint32_t)__popcll(prim_m));
+      n_hit.add((uint32_t)__popcll(prim_m & hit_m));
+      n_shadow.add((uint32_t)__popcll(cons_m & ballot(phase == kShadow)));
     }
     ev_prim = cons && phase == kPrimary, ev_shadow = cons && phase == kShadow;
     const bool tap = cons && !ev_prim && !ev_shadow;  // normal taps k.xyy, k.yyx, k.yxy, k.xxx
@@ -910,7 +988,7 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
     const bool step = (ev_prim || ev_shadow) && !hit;  // march on: t += d, it++
     const float t_next = t + de;
     const uint32_t it_next = it + 1u;
-    const bool more = it_next < f.max_steps && t_next < kMaxTotalDistance;
+    const bool more = it_next < max_steps && t_next < kMaxTotalDistance;
     t = step ? t_next : t;
     it = step ? it_next : it;
     psteps = ev_hit ? it : psteps;
@@ -961,7 +1039,7 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
       FRM_SUB_END(3);
     }
     }  // !lean
-    if constexpr (kLeanPass) n_bail += count(ev_bail);
+    if constexpr (kLeanPass) n_bail.add((uint32_t)count(ev_bail));
     if constexpr (RES) {  // drained slots whose last pixels left the lanes
       const uint32_t gone = rw_get(rw, kRwGone);
       if (gone) ring_settle(ring_lds, rw, gone, pix);
@@ -975,18 +1053,31 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
     if (want != 0 && !exhausted) {
       if (slots_used == kChunk) {
         uint32_t base = kIdle;
+        // the launch's pixels, frames and queue sizes as this block sees them
+        uint32_t f_npix = a.npix, f_batch = a.batch, f_total = total, f_nchunks = nchunks, f_nhead = nhead;
+        if constexpr (kQueueReload) {  // loaded and worked out here (the empty asm: not hoisted out of the loop)
+          typedef const __attribute__((address_space(4))) KernelArgs* kernarg_ptr;
+          kernarg_ptr ka = (kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+          asm volatile("" : "+s"(ka));
+          f_npix = ka->npix;
+          f_batch = ka->batch;
+          f_total = multi ? f_batch * ((f_npix + kChunk - 1u) / kChunk) * kChunk : f_npix;
+          f_nchunks = (f_total + kChunk - 1u) / kChunk;
+          f_nhead = f_nchunks / kQueueHeadDiv;
+        }
         if constexpr (RES) {
           base = ring_claim(ring_lds, rw, cam_lds, nchunks, nhead, pix, &r_slot);
         } else {
+        constexpr drain_t kOne = 1, kAllParts = (drain_t)((1ull << kQueueParts) - 1ull);
         // the head of the order (its most expensive chunks) from the shared counter
         if (!(drained >> kQueueParts)) {
           uint32_t j = 0;
           if (lane == 0) j = atomicAdd(a.queue + kQueueParts * kQueuePartWords, 1u);
           j = uniform(__shfl(j, 0, 64));
-          if (j < nhead)
+          if (j < f_nhead)
             base = j * kChunk;
           else
-            drained |= 1ull << kQueueParts;
+            drained |= kOne << kQueueParts;
         }
         // then chunk j of the XCD's partition x is queue chunk nhead + j * kQueueParts + x; a
         // drained partition passes the wave on to the next one
@@ -994,13 +1085,13 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
           uint32_t j = 0;
           if (lane == 0) j = atomicAdd(a.queue + part * kQueuePartWords, 1u);
           j = uniform(__shfl(j, 0, 64));
-          const uint32_t c = nhead + j * kQueueParts + part;
-          if (c < nchunks) {
+          const uint32_t c = f_nhead + j * kQueueParts + part;
+          if (c < f_nchunks) {
             base = c * kChunk;
             break;
           }
-          drained |= 1ull << part;
-          if ((drained & ((1ull << kQueueParts) - 1ull)) == (1ull << kQueueParts) - 1ull) break;
+          drained |= kOne << part;
+          if ((drained & kAllParts) == kAllParts) break;
           do part = (part + 1u) % kQueueParts;
           while ((drained >> part) & 1u);
         }
@@ -1019,7 +1110,7 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
           // frame's cost keys, frm_sched.hip), row-major without history
           uint32_t p = kIdle;
           v3 ray = mk(0.f, 0.f, 0.f);
-          uint32_t pos0 = base, lim = total;
+          uint32_t pos0 = base, lim = f_total;
           // RES: the chunk's frame's camera rows (wave-uniform, SGPRs): one LDS word per lane, then
           // lane reads (twelve loads into VGPRs before their readfirstlanes pushed the march state
           // into scratch). The load is pinned here, where every lane runs: the compiler would
@@ -1034,9 +1125,9 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
           }
           if constexpr (multi) {
             const uint32_t c = base / kChunk;
-            chunk_frame = uniform(c % a.batch);
-            pos0 = (c / a.batch) * kChunk;
-            lim = a.npix;
+            chunk_frame = uniform(c % f_batch);
+            pos0 = (c / f_batch) * kChunk;
+            lim = f_npix;
           }
           if (pos0 + lane < lim) {
             const uint32_t lp =
@@ -1057,7 +1148,7 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
               ray = camera_ray(f, x, y);
             p = (RES ? r_slot * a.rec_stride : chunk_frame * a.rec_stride) + lp;  // the pixel's record index
           }
-          if constexpr (!RES) n_pix += count(p != kIdle);
+          if constexpr (!RES) n_pix.add((uint32_t)count(p != kIdle));
           chunk_rays[wave][lane] = make_float4(ray.x, ray.y, ray.z, __uint_as_float(p));
           __builtin_amdgcn_wave_barrier();
           slots_used = 0;
@@ -1112,7 +1203,11 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
       // lanes): the point itself. Tested here again: the lean flag carried across the refill is a
       // lane mask that the register allocator parks in two VGPR lanes, four lane moves per pass.
       bool no_tap = false;
+#if FRM_LEAN_CARRY  // (the lean decision carried across the refill instead: round 9, measured)
+      if constexpr (kLeanPass) no_tap = lean;
+#else
       if constexpr (kLeanPass) no_tap = ballot(phase - kTap0 <= kTap3 - kTap0) == 0;
+#endif
       if (no_tap) {
         q = r;
       } else {
@@ -1140,10 +1235,10 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
     // work counters (frm_stats); a ring grid's frames report none (frm_render with stats renders
     // outside the ring), so it keeps no counters
     if constexpr (!RES && !kLeanPass) {
-      n_prim += count(ev_prim);
-      n_hit += count(ev_hit);
-      n_shadow += count(ev_shadow);
-      n_bail += count(ev_bail);
+      n_prim.add((uint32_t)count(ev_prim));
+      n_hit.add((uint32_t)count(ev_hit));
+      n_shadow.add((uint32_t)count(ev_shadow));
+      n_bail.add((uint32_t)count(ev_bail));
     }
 #ifdef FRM_STAMPS
     stamp_service += __builtin_amdgcn_s_memtime() - stamp0;
@@ -1178,7 +1273,7 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
       for (int k = 0; k < 4; ++k) r[11 + k] = stamp_sub[k];
       r[15] = n_lean;  // service passes that took the lean path
       r[0] = n_loop;
-      r[1] = n_body;
+      r[1] = n_body.value();
       r[2] = n_service;
       r[3] = stamp_service;
       r[4] = __builtin_amdgcn_s_memtime() - stamp_begin;
@@ -1192,12 +1287,18 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
 #ifdef FRM_COUNT_EXACT
     atomicAdd(&a.counters[7], (unsigned long long)((n_dbg_total << 32) | n_dbg_exact));
 #endif
+    // the counts without the debug start value, in 64 bits; the value is read again here (a
+    // volatile load of the kernel argument) so that it holds no register across the loops
+    typedef const volatile __attribute__((address_space(4))) KernelArgs* kernarg_ptr;
+    const uint64_t c0 = ((kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr())->counter_start;
+    const uint64_t c_hit = n_hit.value() - c0;
+    uint64_t c_prim = n_prim.value() - c0, c_body = n_body.value() - c0, c_bail = n_bail.value() - c0;
     if (blockIdx.x == 0 && wave == 0) {  // the launch's skipped steps 0 (KernelArgs::first_counts)
-      n_prim += a.first_counts[0];
-      n_body += a.first_counts[1];
-      n_bail += a.first_counts[2];
+      c_prim += a.first_counts[0];
+      c_body += a.first_counts[1];
+      c_bail += a.first_counts[2];
     }
-    unsigned long long v[7] = {n_pix, n_hit, n_prim, n_shadow, 4ull * n_hit, n_body, n_bail};
+    unsigned long long v[7] = {n_pix.value() - c0, c_hit, c_prim, n_shadow.value() - c0, 4ull * c_hit, c_body, c_bail};
 #pragma unroll
     for (int k = 0; k < 7; ++k)
       if (v[k]) atomicAdd(&a.counters[k], v[k]);
