@@ -76,7 +76,7 @@ constexpr uint32_t kFirstSkip = 1u << 31, kFirstBail = 1u << 30, kFirstCostMask 
 constexpr uint32_t kRankWords = 512;  // one launch's key_hist: 256 counts + 256 cursors
 constexpr uint32_t kShadeBlockPixels = 4096;  // shade_pass / rank_pass: local pixels per 256-thread block
 
-// ---- resident frame ring (frm_api.hip resident_render; march_persistent<..., RES>) ----------
+// ---- resident frame ring (frm_ring.hip ring_render; march_persistent<..., RES>) ----------
 // Single-frame frm_render calls on a context with frames in flight post their frames to a ring
 // of kRingSlots-or-fewer slots instead of launching a grid per frame. One persistent grid serves
 // the ring for as long as frames keep arriving: its march waves claim the oldest posted frame's
@@ -182,7 +182,7 @@ struct KernelArgs {
   uint32_t batch;
   uint32_t rec_stride;            // records per frame
   uint32_t out_stride;            // packed RGBA8 words per frame
-  // Fused scheduling (frm_api.hip launch; nullptr: off). The shading pass counts the cost keys
+  // Fused scheduling (frm_launch.hip launch; nullptr: off). The shading pass counts the cost keys
   // of the launch's last frame into key_hist[0..255]; rank_pass then ranks the local pixels by
   // descending key into order_out (the 8-bit counting sort the hipcub path does: bucket bases from
   // that histogram, per-block ranges reserved through the cursors key_hist[256..511]), the fetch

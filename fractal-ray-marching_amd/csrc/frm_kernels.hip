@@ -290,7 +290,7 @@ static hipError_t launch_family(const KernelArgs& args, KernelKind kind, int cu_
   return hipGetLastError();
 }
 
-// A resident ring grid (frm_api.hip resident_render): the occupancy limit of the RES instantiation
+// A resident ring grid (frm_ring.hip ring_launch): the occupancy limit of the RES instantiation
 // (the Mandelbulb's with per-lane powers: ring frames differ in time) over every CU, the first
 // args.ring.service_waves workgroups serving the ring (frm_render_kernels.h ring_service).
 template <uint32_t FAM, bool ITERS>

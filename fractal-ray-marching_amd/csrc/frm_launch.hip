@@ -1,0 +1,396 @@
+// frm_launch.hip — what every render path of a context shares: the pool buffers that follow the
+// frame size, slot framebuffers and streams, a launch's arguments, launch(), the steps of a frame.
+#include "frm_ctx.h"
+
+// Device memory of the context pool, allocated / released in the order of stream s: a block
+// released on s is reused only by work ordered after everything enqueued on s before the release.
+int dev_alloc(frm_ctx* ctx, void** p, size_t bytes, hipStream_t s) {
+  FRM_HIP(ctx, hipMallocFromPoolAsync(p, bytes, ctx->pool, s));
+  return FRM_OK;
+}
+int dev_release(frm_ctx* ctx, void* p, hipStream_t s) {
+  if (p) FRM_HIP(ctx, hipFreeAsync(p, s));
+  return FRM_OK;
+}
+// Makes b hold at least `bytes`: nothing when it already does (outside the first frame of a size,
+// the steady state), else the old block is released and the new one allocated from owner's pool,
+// both in the order of stream s. The caller has ordered the old block's last use before s.
+int pool_grow(frm_ctx* owner, PoolBuf& b, size_t bytes, hipStream_t s) {
+  if (b.cap >= bytes) return FRM_OK;
+  if (int rc = dev_release(owner, b.p, s)) return rc;
+  b = PoolBuf{};
+  if (int rc = dev_alloc(owner, (void**)&b.p, bytes, s)) return rc;
+  b.cap = bytes;
+  return FRM_OK;
+}
+// The ShadeTail records of a slot's persistent-kernel scratch: after the ShadeGeom records of the
+// capacity the block was allocated for (not of the current launch's need).
+ShadeTail* record_tails(const PoolBuf& records) {
+  return reinterpret_cast<ShadeTail*>(records.p + records.cap / kRecordBytes * sizeof(ShadeGeom));
+}
+
+// Slot sl's framebuffer for a frame of `bytes`, grown on the slot stream (renders and synchronous
+// readback use it there; an asynchronous readback on the copy stream is awaited first: frm_render /
+// frm_resize wait, select_fb).
+int ensure_fb(frm_ctx* ctx, Slot& sl, size_t bytes) {
+  return pool_grow(ctx, sl.fbs[sl.fb_idx], with_headroom(bytes), sl.stream);
+}
+// Makes fbs[i] the slot's current framebuffer, its last asynchronous readback ordered before
+// everything enqueued on the slot stream from here on.
+int select_fb(frm_ctx* ctx, Slot& sl, uint32_t i) {
+  sl.fb_idx = i;
+  if (sl.fb_read_pending[i]) {
+    FRM_HIP(ctx, hipStreamWaitEvent(sl.stream, sl.fb_read[i], 0));
+    sl.fb_read_pending[i] = false;
+  }
+  return FRM_OK;
+}
+
+// The resolved image that goes with the slot's current framebuffer, for an output frame of `bytes`,
+// grown on the slot stream like the framebuffer (ensure_fb; select_fb has ordered its readers).
+int ensure_res(frm_ctx* ctx, Slot& sl, size_t bytes) {
+  return pool_grow(ctx, sl.res[sl.fb_idx], with_headroom(bytes), sl.stream);
+}
+// The scratch of the slot's adaptive pass for a frame of npix pixels, grown on the slot stream (the
+// slot's last pass ran there).
+static int ensure_refine(frm_ctx* ctx, Slot& sl, size_t npix) {
+  if (!sl.refine_ctl)
+    if (int rc = dev_alloc(ctx, (void**)&sl.refine_ctl, kRefineCtlBytes, sl.stream)) return rc;
+  return pool_grow(ctx, sl.refine_list, npix * sizeof(uint32_t), sl.stream);
+}
+// The second image of the slot's current framebuffer, on the slot stream, after the frame is
+// complete there: the box resolve of a supersampled context, or the adaptive frame of an adaptive
+// one (the edge pass over the frame, then the samples of its refined pixels; their work is added
+// to the context's counters). The slot's `done` event is recorded again, so that it covers it.
+int resolve_frame(frm_ctx* ctx, Slot& sl) {
+  sl.adaptive[sl.fb_idx] = false;
+  if (ctx->supersample == 1u && ctx->adaptive == 1u) return FRM_OK;
+  if (int rc = ensure_res(ctx, sl, (size_t)ctx->out_width * ctx->out_height * 4u)) return rc;
+  uint8_t* res = sl.res[sl.fb_idx].p;
+  if (ctx->adaptive > 1u) {  // (excludes supersampling: the render size is the output size)
+    if (int rc = ensure_refine(ctx, sl, (size_t)ctx->width * ctx->height)) return rc;
+    FrameUniforms f;
+    compute_frame_uniforms(ctx->params, ctx->adaptive * ctx->width, ctx->adaptive * ctx->height, ctx->max_steps, &f);
+    FRM_HIP(ctx, launch_adaptive(f, ctx->scene, sl.fb(), res, ctx->width, ctx->height, ctx->adaptive,
+                                 ctx->edge_threshold, (uint32_t*)sl.refine_list.p, sl.refine_ctl, ctx->counters,
+                                 ctx->cu_count, sl.stream));
+    sl.adaptive[sl.fb_idx] = true;
+    sl.refine_w = ctx->width;
+    sl.refine_h = ctx->height;
+  } else {
+    FRM_HIP(ctx, launch_resolve(sl.fb(), res, ctx->out_width, ctx->out_height, ctx->supersample, sl.stream));
+  }
+  FRM_HIP(ctx, hipEventRecord(sl.done, sl.stream));
+  return FRM_OK;
+}
+// What the presentation paths read of a slot: out_width x out_height texels.
+const uint8_t* shown(const frm_ctx* ctx, const Slot& sl) {
+  return ctx->supersample > 1u || sl.adaptive[sl.fb_idx] ? sl.res[sl.fb_idx].p : sl.fb();
+}
+
+static uint32_t num_bands(uint32_t height, uint32_t band_rows) { return (height + band_rows - 1) / band_rows; }
+
+// Rows produced by bands first, first+stride, ... below num_bands (the last band of the
+// frame may be short, but a band buffer always reserves band_rows rows for it).
+uint32_t band_local_rows(uint32_t height, uint32_t band_rows, uint32_t first, uint32_t stride) {
+  uint32_t nb = num_bands(height, band_rows);
+  if (first >= nb) return 0;
+  uint32_t count = (nb - 1 - first) / stride + 1;
+  return count * band_rows;
+}
+
+// Local rows that hold frame rows: all but the missing rows of a short last band, which
+// can only be this launch's last band (its local rows are then a prefix).
+static uint32_t band_valid_rows(uint32_t height, const BandGeometry& g) {
+  if (g.local_rows == 0) return 0;
+  const uint32_t last = g.first_band + (g.local_rows / g.band_rows - 1u) * g.band_stride;
+  const uint32_t end = (last + 1u) * g.band_rows;  // one past its last global row
+  return end > height ? g.local_rows - (end - height) : g.local_rows;
+}
+
+// Band height of a group's row split: the smallest height >= 16 that splits the frame into a
+// multiple of n bands (else 16), so interleaved bands balance the devices (frm/tiling.py).
+uint32_t group_band_rows(uint32_t height, uint32_t n) {
+  for (uint32_t br = 16; br <= height; ++br)
+    if (height % br == 0 && (height / br) % n == 0) return br;
+  return 16;
+}
+
+// A launch of the context's frame size with the given parameters and their scene uniforms.
+KernelArgs make_args(const frm_ctx* ctx, const frm_parameters& params, const SceneUniforms& scene, uint8_t* dst,
+                     unsigned long long* counters, uint32_t band_rows, uint32_t first, uint32_t stride,
+                     uint32_t local_rows) {
+  KernelArgs a;
+  memset(&a, 0, sizeof(a));
+  compute_frame_uniforms(params, ctx->width, ctx->height, ctx->max_steps, &a.f);
+  a.s = scene;
+  a.g.band_rows = band_rows;
+  a.g.first_band = first;
+  a.g.band_stride = stride;
+  a.g.local_rows = local_rows;
+  a.out = (uint32_t*)dst;
+  a.counters = counters;
+  a.npix = band_valid_rows(ctx->height, a.g) * ctx->width;
+  a.service_min = ctx->service_min;
+  a.batch = 1;
+  a.rec_stride = local_rows * ctx->width;
+  a.out_stride = local_rows * ctx->width;
+  memcpy(a.cams[0].row, a.f.row, sizeof(a.f.row));  // a single frame is a batch of one
+  a.cams[0].origin = a.f.origin;
+  return a;
+}
+
+KernelKind kernel_for(const frm_ctx* ctx, uint64_t pixels) {
+  if (ctx->flags & FRM_FLAG_SIMPLE_KERNEL) return kKernelSimple;
+  if (ctx->flags & FRM_FLAG_PERSISTENT_KERNEL) return kKernelPersistent;
+  return pixels < kSimplePixelsPerCu * (uint64_t)ctx->cu_count ? kKernelSimple : kKernelPersistent;
+}
+
+// Waits (host) until the slot's last launch has completed.
+int wait_slot(frm_ctx* ctx, Slot& sl) {
+  if (sl.pending) {
+    FRM_HIP(ctx, hipEventSynchronize(sl.done));
+    sl.pending = false;
+  }
+  return FRM_OK;
+}
+
+int synchronize_all(frm_ctx* ctx) {
+  for (uint32_t i = 0; i < ctx->nslots; ++i) {
+    Slot& sl = ctx->slots[i];
+    if (sl.stream) FRM_HIP(ctx, hipStreamSynchronize(sl.stream));
+    int rc = wait_slot(ctx, sl);
+    if (rc) return rc;
+  }
+  return FRM_OK;
+}
+
+// The stream frm_render uses for slot i (created on first use: a context with one frame in
+// flight never creates more than the context stream).
+// Slots > 0 need a hardware queue of their own to overlap: HIP maps streams onto at most
+// GPU_MAX_HW_QUEUES queues per process (4 by default) and hands the least-used one out again,
+// and two frames whose streams share a queue never overlap. Plain
+// non-blocking streams get distinct queues while the pool has room (bench.py raises the limit to
+// 16); FRM_SLOT_STREAMS=cumask asks for CU-masked streams, which the runtime never pools.
+static hipStream_t own_queue_stream(int device) {
+  hipDeviceProp_t prop;
+  // default: a pooled non-blocking stream. "cumask": a CU-masked stream, which gets a hardware queue
+  // of its own but is a BLOCKING stream (hipExtStreamCreateWithCUMask takes no flags): it
+  // synchronises with the legacy null stream (torch's default stream, synchronous hipMemcpy), so
+  // it is opt-in for hosts that never use that stream
+  const char* kind = getenv("FRM_SLOT_STREAMS");
+  const bool cumask = kind && strcmp(kind, "cumask") == 0;
+  if (cumask && hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) {
+    const uint32_t words = (uint32_t)(prop.multiProcessorCount + 31) / 32u;
+    uint32_t mask[64];
+    if (words <= 64u) {
+      for (uint32_t w = 0; w < words; ++w) mask[w] = 0xFFFFFFFFu;
+      hipStream_t s = nullptr;
+      if (hipExtStreamCreateWithCUMask(&s, words, mask) == hipSuccess) return s;
+    }
+  }
+  hipStream_t s = nullptr;
+  return hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess ? s : nullptr;
+}
+
+int slot_stream(frm_ctx* ctx, uint32_t i, hipStream_t* out) {
+  Slot& sl = ctx->slots[i];
+  if (!sl.stream && !(sl.stream = own_queue_stream(ctx->device)))
+    return fail(ctx, FRM_ERR_HIP, "stream creation failed for render slot %u", i);
+  *out = sl.stream;
+  return FRM_OK;
+}
+
+// The fetch order of persistent launch `a` (stream s, slot si's scratch) and its scheduling history.
+static int schedule_launch(frm_ctx* ctx, uint32_t si, KernelArgs& a, hipStream_t s) {
+  Slot& sl = ctx->slots[si];
+  // pixel scheduling: fetch this launch's pixels by the cost the slot recorded last time
+  // for the same geometry (most expensive first)
+  const uint32_t npix = a.npix;
+  const uint64_t key = ((uint64_t)a.f.width << 40) ^ ((uint64_t)a.g.local_rows << 20) ^
+                       ((uint64_t)a.g.band_rows << 8) ^ ((uint64_t)a.g.first_band << 4) ^ a.g.band_stride ^
+                       ((uint64_t)a.f.height << 52);
+  // a whole frame (not a rank's bands): its keys can seed a resized whole frame's order
+  const bool whole = a.g.first_band == 0 && a.g.band_stride == 1 && npix == a.f.width * a.f.height;
+  const bool same = sl.sched_history && key == sl.sched_key;
+  const bool rescale = !same && sl.sched_history && sl.sched_whole && whole;
+  // a slot without history of this geometry takes another slot's keys: with frames in
+  // flight, every slot's first launch would otherwise fetch in row-major order
+  int donor = -1;
+  if (!same && !rescale)
+    for (uint32_t j = 0; j < ctx->nslots && donor < 0; ++j) {
+      const Slot& o = ctx->slots[j];
+      if (j != si && o.sched_history && o.sched_key == key && o.sched_cap >= npix) donor = (int)j;
+    }
+  if (npix > sl.sched_cap) {
+    // stream-ordered like the records; a donor's copy of these keys was awaited above
+    uint8_t* old_keys = sl.sched_keys;  // kept until a resize has resampled it
+    int rc = FRM_OK;
+    for (void* b : {(void*)sl.sched_iota, (void*)sl.sched_order, sl.sched_temp})
+      if ((rc = dev_release(ctx, b, s))) return rc;
+    if (!rescale && (rc = dev_release(ctx, old_keys, s))) return rc;
+    sl.sched_iota = sl.sched_order = nullptr;
+    sl.sched_keys = nullptr;
+    sl.sched_temp = nullptr;
+    sl.sched_cap = 0;
+    sl.sched_temp_bytes = schedule_temp_bytes(npix);
+    if ((rc = dev_alloc(ctx, (void**)&sl.sched_iota, (size_t)npix * sizeof(uint32_t), s)) ||
+        (rc = dev_alloc(ctx, (void**)&sl.sched_order, (size_t)npix * sizeof(uint32_t), s)) ||
+        (rc = dev_alloc(ctx, (void**)&sl.sched_keys, (size_t)npix * 2, s)) ||
+        (rc = dev_alloc(ctx, &sl.sched_temp, sl.sched_temp_bytes ? sl.sched_temp_bytes : 16, s)))
+      return rc;
+    FRM_HIP(ctx, fill_iota(sl.sched_iota, npix, s));
+    sl.sched_cap = npix;
+    if (rescale) {
+      FRM_HIP(ctx, rescale_keys(old_keys, sl.sched_w, sl.sched_h, sl.sched_keys, a.f.width, a.f.height, s));
+      if ((rc = dev_release(ctx, old_keys, s))) return rc;  // after the resample reads it
+    }
+  } else if (rescale) {
+    // resample into the sort's output half, then back (the map is read and written)
+    uint8_t* tmp = sl.sched_keys + sl.sched_cap;
+    FRM_HIP(ctx, rescale_keys(sl.sched_keys, sl.sched_w, sl.sched_h, tmp, a.f.width, a.f.height, s));
+    FRM_HIP(ctx, hipMemcpyAsync(sl.sched_keys, tmp, npix, hipMemcpyDeviceToDevice, s));
+  }
+  if (donor >= 0) {  // keys order fetches only, never a pixel's bytes
+    Slot& dn = ctx->slots[donor];
+    if (dn.pending && dn.last_stream != s) FRM_HIP(ctx, hipStreamWaitEvent(s, dn.done, 0));
+    // an earlier reader's copy on another stream: order this copy after it, so the one
+    // keys_read event recorded below covers every copy the donor's next launch must await
+    if (dn.keys_reader && dn.keys_reader != s) FRM_HIP(ctx, hipStreamWaitEvent(s, dn.keys_read, 0));
+    FRM_HIP(ctx, hipMemcpyAsync(sl.sched_keys, dn.sched_keys, npix, hipMemcpyDeviceToDevice, s));
+    FRM_HIP(ctx, hipEventRecord(dn.keys_read, s));  // the donor's next launch waits for this copy
+    dn.keys_reader = s;
+  }
+  // the steady state: the slot's last launch (same geometry) has already ranked its pixels and
+  // reset this launch's counters in its shading pass, so nothing runs between the two launches
+  const bool fused = same && sl.order_ready && sl.order_key == key;
+  uint32_t* half = sl.rank_words + sl.rank_half * kRankWords;
+  if (!fused) {
+    const bool history = same || rescale || donor >= 0;
+    FRM_HIP(ctx, schedule_pixels(npix, history, sl.sched_keys, sl.sched_keys + sl.sched_cap,
+                                 sl.sched_iota, sl.sched_order, sl.sched_temp, sl.sched_temp_bytes, s));
+    FRM_HIP(ctx, hipMemsetAsync(sl.queue, 0, kQueueDebugWord * sizeof(unsigned int), s));
+    FRM_HIP(ctx, hipMemsetAsync(half, 0, kRankWords * sizeof(uint32_t), s));
+  }
+  // runtime-reloaded kernels may not rank (edited sources): the next launch sorts again
+  const bool rank = ctx->reloaded == nullptr && ctx->fused_sched;
+  a.key_hist = rank ? half : nullptr;
+  a.key_hist_next = sl.rank_words + (sl.rank_half ^ 1u) * kRankWords;
+  a.order_out = sl.sched_order;
+  sl.order_ready = false;  // set by launch() once the launch is enqueued
+  sl.order_key = key;
+  a.pixel_order = sl.sched_order;
+  a.pixel_key = sl.sched_keys;
+  sl.sched_key = key;
+  sl.sched_history = true;
+  sl.sched_whole = whole;
+  sl.sched_w = a.f.width;
+  sl.sched_h = a.f.height;
+  sl.sched_npix = npix;
+  return FRM_OK;
+}
+
+static int inflight_blocks_per_cu(uint32_t frames_in_flight) {
+  return frames_in_flight <= 2u ? kInflightBlocksPerCu : (int)(2u * kInflightBlocksPerCu / frames_in_flight);
+}
+
+// Enqueues one render launch on stream s with the scratch of the context's next slot.
+// Stream order covers a slot reused on the same stream; a slot last used on another
+// stream is awaited on the device (hipStreamWaitEvent), so callers may rotate streams.
+int launch(frm_ctx* ctx, KernelArgs a, hipStream_t s) {
+  if (a.g.local_rows == 0) return FRM_OK;
+  const uint32_t si = ctx->next_slot;
+  Slot& sl = ctx->slots[si];
+  if (sl.pending && sl.last_stream != s) FRM_HIP(ctx, hipStreamWaitEvent(s, sl.done, 0));
+  if (sl.keys_reader) {  // another slot's launch read this slot's keys: they are rewritten below
+    if (sl.keys_reader != s) FRM_HIP(ctx, hipStreamWaitEvent(s, sl.keys_read, 0));
+    sl.keys_reader = nullptr;
+  }
+  const KernelKind kind = kernel_for(ctx, a.npix);
+  a.queue = sl.queue;
+  if (kind == kKernelPersistent) {
+    // grows outside the steady state (first frame of a size); stream-ordered: s runs after the
+    // slot's last launch (awaited above when on another stream)
+    const size_t need = (size_t)a.g.local_rows * a.f.width * a.batch;
+    if (int rc = pool_grow(ctx, sl.records, need * kRecordBytes, s)) return rc;
+    a.geom = reinterpret_cast<ShadeGeom*>(sl.records.p);
+    a.tails = record_tails(sl.records);
+    if (int rc = schedule_launch(ctx, si, a, s)) return rc;
+    unsigned int* dbg = sl.queue + kQueueDebugWord;
+    a.debug = (unsigned long long*)dbg;  // the diagnostic words after the partition counters
+#ifdef FRM_STAMPS
+    FRM_HIP(ctx, hipMemsetAsync(dbg, 0, 16, s));
+    FRM_HIP(ctx, hipMemsetAsync(dbg + 4, 0xff, 16, s));  // atomicMin slots
+    FRM_HIP(ctx, hipMemsetAsync(dbg + 8, 0, 8, s));
+#endif
+  }
+  if (kind != kKernelPersistent) sl.order_ready = false;
+  // Single-frame persistent launches with frames in flight run a grid of 4 waves per SIMD (16
+  // one-wave workgroups per CU) instead of the occupancy limit (8 for the Mandelbulb): two frames'
+  // grids then share the GPU, each frame's shading and ranking find room beside the next frame's
+  // grid, and one frame's tail runs beside the other's bulk. Measured (profiles/round5/dropin_bpc):
+  // the drop-in loop 9.11-9.18 -> 8.57-8.60 ms (fixed pose), 10.08-10.13 -> 9.29-9.32 (HEADLINE_FLY);
+  // multi-frame launches (one queue for all their frames) keep the full grid (8-way rank share
+  // 1.098 ms/frame full, 1.117 at 12).
+  int blocks_cap = 0;
+  if (a.batch == 1) {
+    if (ctx->nslots >= 2 && a.npix <= kInflightCapPixels)
+      blocks_cap = inflight_blocks_per_cu(ctx->nslots);
+    else if (ctx->nslots == 1)
+      blocks_cap = kLoneFrameBlocksPerCu;
+  }
+  FRM_HIP(ctx, launch_render(a, kind, ctx->cu_count, s, ctx->reloaded, blocks_cap));
+  if (a.key_hist) {
+    sl.order_ready = true;
+    sl.rank_half ^= 1u;
+  }
+  FRM_HIP(ctx, hipEventRecord(sl.done, s));
+  sl.seq = ++ctx->launch_seq;
+  sl.pending = true;
+  sl.last_stream = s;
+  ctx->next_slot = (si + 1u) % ctx->nslots;
+  return FRM_OK;
+}
+
+// ---- the steps of a frame (frm_render, group_render; the ring writes the last two) ----------
+
+// Claims the context's next slot for a frame of the context's size: its stream, and the other
+// framebuffer of the slot: the last one may still be read back (copy stream); this one's readback
+// (two renders of the slot ago) is awaited on the slot stream, long done.
+int begin_frame(frm_ctx* ctx, Slot** out_slot, hipStream_t* out_stream) {
+  const uint32_t si = ctx->next_slot;
+  Slot& sl = ctx->slots[si];
+  *out_slot = &sl;
+  if (int rc = slot_stream(ctx, si, out_stream)) return rc;
+  if (int rc = select_fb(ctx, sl, sl.fb_idx ^ 1u)) return rc;
+  return ensure_fb(ctx, sl, (size_t)ctx->width * ctx->height * 4u);
+}
+
+// A frame with stats, on stream s (the caller has drained the context: the counters must hold this
+// frame alone). Before its launches: the counters zeroed and ev_start. After them: ev_stop, then
+// (the host waits for s) the context's counters of the frame and its time on the device.
+int stats_begin(frm_ctx* ctx, hipStream_t s) {
+  FRM_HIP(ctx, hipMemsetAsync(ctx->counters, 0, FRM_NUM_COUNTERS * sizeof(unsigned long long), s));
+  FRM_HIP(ctx, hipEventRecord(ctx->ev_start, s));
+  return FRM_OK;
+}
+int stats_end(frm_ctx* ctx, hipStream_t s, uint64_t* out_counters, float* out_ms) {
+  FRM_HIP(ctx, hipEventRecord(ctx->ev_stop, s));
+  FRM_HIP(ctx, hipMemcpyAsync(out_counters, ctx->counters, FRM_NUM_COUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  FRM_HIP(ctx, hipStreamSynchronize(s));
+  FRM_HIP(ctx, hipEventElapsedTime(out_ms, ctx->ev_start, ctx->ev_stop));
+  return FRM_OK;
+}
+
+// The frame the presentation paths (frm_read_frame, frm_present, their async forms) see from here
+// on: slot sl's last launch.
+void show_slot(frm_ctx* ctx, const Slot& sl) {
+  ctx->last_slot = (uint32_t)(&sl - ctx->slots);
+  ctx->render_seq = sl.seq;
+  ctx->last_is_ring = false;
+}
+// The parameters of the frame just rendered or posted, which frm_debug_trace replays.
+void keep_render_params(frm_ctx* ctx) {
+  ctx->render_params = ctx->params;
+  ctx->render_scene = ctx->scene;
+}

@@ -217,7 +217,7 @@ __device__ __forceinline__ void ring_refresh(const RingArgs& r, RingView& v) {
 // A march wave with nothing left to claim up to v.limit closes the grid: the first to get there
 // publishes `closed` to the host, waits for that store, reads `posted` once more and fixes the last
 // frame the grid serves; every other wave waits for that limit. Frames posted later belong to the
-// next grid, which the host launches when it sees `closed` after its own post (frm_api.hip
+// next grid, which the host launches when it sees `closed` after its own post (frm_ring.hip
 // ring_render: each side stores, then loads the other's word, so one of them sees the other's store).
 __device__ __forceinline__ void ring_close(const RingArgs& r, RingView& v) {
   uint32_t lim = 0, ok = 1;
@@ -588,7 +588,7 @@ __device__ __forceinline__ void ring_idle() {
 // A ring grid's service wave: shades, ranks and publishes the grid's frames as their marches
 // complete (oldest first, any of the `slots` frames in flight), until the grid has closed and
 // every frame up to its limit is done. Sleeps between polls; gives up after kRingWatchdogTicks
-// without progress (the host then reports the frame as never completed, frm_api.hip).
+// without progress (the host then reports the frame as never completed, frm_ring.hip).
 template <uint32_t FAM>
 __device__ __noinline__ void ring_service(const KernelArgs& a, uint32_t* cnt) {
   const RingArgs& R = a.ring;

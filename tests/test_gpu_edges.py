@@ -58,7 +58,7 @@ def test_edge_case_trace(frm_lib, oracle, case):
     assert same.all(), f"{case.name}: {np.sum(~same.all(axis=-1))} hit pixels differ, fields {sorted(set(np.nonzero(~same)[1].tolist()))}"
 
 
-WAVES_PER_CU = 32  # the persistent kernel's ceiling of one-wave workgroups per CU (frm_api.hip)
+WAVES_PER_CU = 32  # the persistent kernel's ceiling of one-wave workgroups per CU (frm_ctx.h)
 
 
 def mixed_frame_size(cus, frames=4):

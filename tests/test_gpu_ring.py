@@ -1,4 +1,4 @@
-"""The resident frame ring (frm_api.hip ring_render, march_persistent<..., RES>): single-frame
+"""The resident frame ring (frm_ring.hip ring_render, march_persistent<..., RES>): single-frame
 frm_render calls without stats on a context with frames in flight are served by one persistent grid
 that marches the posted frames in order and shades each as its last pixel finishes. Every frame of
 every loop form below must equal the oracle's render of its own Parameters, as the reference's

@@ -17,10 +17,5 @@ if [ -n "$PATCH" ]; then
   cp csrc/* "$SRC/"
   (cd "$SRC" && patch -s -p3 < "$ROOT/$PATCH")
 fi
-OBJ=build/obj_$NAME
-mkdir -p ab
-make -s CSRC="$SRC" OBJDIR=$OBJ EXTRA_HIPFLAGS="$FLAGS" $MAKEVARS ${SCHEDFLAGS+SCHEDFLAGS="$SCHEDFLAGS"} $OBJ/frm_kernels.o $OBJ/frm_api.o \
-  $OBJ/frm_sched.o $OBJ/frm_host.o $OBJ/frm_reload.o
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ab/$NAME.so $OBJ/frm_kernels.o \
-  $OBJ/frm_api.o $OBJ/frm_sched.o $OBJ/frm_host.o $OBJ/frm_reload.o -lhiprtc -lrccl
+make -s CSRC="$SRC" OBJDIR=build/obj_$NAME LIB=ab/$NAME.so EXTRA_HIPFLAGS="$FLAGS" $MAKEVARS ${SCHEDFLAGS+SCHEDFLAGS="$SCHEDFLAGS"} ab/$NAME.so
 echo "ab/$NAME.so"
