@@ -153,6 +153,10 @@ int create_one(const frm_config* config, int device, frm_ctx** out_ctx) {
     long v = strtol(env, nullptr, 10);
     if (v >= 1 && v <= 64) ctx->service_min = (uint32_t)v;
   }
+  if (const char* env = getenv("FRM_SHUTTER_CHUNK")) {  // sub-frames per chunk of frm_render_shutter (tuning, tests)
+    long v = strtol(env, nullptr, 10);
+    if (v >= 1 && v <= (long)FRM_MAX_SHUTTER_SAMPLES) ctx->shutter_chunk = (uint32_t)v;
+  }
   if (int rc = init_one(ctx)) return create_failed(ctx, rc);
   *out_ctx = ctx;
   return FRM_OK;
@@ -233,7 +237,8 @@ int frm_destroy(frm_ctx* ctx) {
     Slot& sl = ctx->slots[i];
     // pool blocks back to the pool (every stream is idle), then the pool itself below
     if (ctx->stream) {
-      for (const PoolBuf* b : {&sl.fbs[0], &sl.fbs[1], &sl.res[0], &sl.res[1], &sl.refine_list, &sl.records, &sl.present_dev})
+      for (const PoolBuf* b : {&sl.fbs[0], &sl.fbs[1], &sl.res[0], &sl.res[1], &sl.refine_list, &sl.records, &sl.present_dev,
+                               &sl.shutter_src, &sl.shutter_acc})
         if (b->p) (void)hipFreeAsync(b->p, ctx->stream);
       for (void* b : {(void*)sl.refine_ctl, (void*)sl.sched_iota, (void*)sl.sched_order, (void*)sl.sched_keys, sl.sched_temp})
         if (b) (void)hipFreeAsync(b, ctx->stream);
@@ -761,6 +766,51 @@ int frm_render_bands(frm_ctx* ctx, uint8_t* dev_dst, size_t dst_bytes, uint32_t 
   return launch(ctx, a, s);
 }
 
+// The frames of one multi-frame launch may differ in camera, and for the Mandelbulb in time (its
+// power, fragment.wgsl:75, is the only time-derived constant): otherwise the same scene uniforms
+// (scene, iterations, time-derived constants). Returns the first frame whose uniforms differ from
+// frame 0's in more than that (0: none); *s0: frame 0's uniforms, powers[k]: frame k's power,
+// *anim: the powers differ.
+static uint32_t batch_uniforms(const frm_ctx* ctx, uint32_t count, const frm_parameters* params, SceneUniforms* s0,
+                               float* powers, bool* anim) {
+  compute_scene_uniforms(params[0], ctx->flags, s0);
+  *anim = false;
+  powers[0] = s0->mb_power;
+  for (uint32_t k = 1; k < count; ++k) {
+    SceneUniforms sk;
+    compute_scene_uniforms(params[k], ctx->flags, &sk);
+    powers[k] = sk.mb_power;
+    if (is_mandelbulb(s0->family) && sk.family == s0->family && sk.mb_power != s0->mb_power) {
+      *anim = true;
+      sk.mb_power = s0->mb_power;
+      sk.mb_power_m1 = s0->mb_power_m1;
+    }
+    if (memcmp(s0, &sk, sizeof(sk)) != 0) return k;
+  }
+  return 0;
+}
+// Whether `count` such frames of a.npix local pixels share one launch; else one launch per frame:
+// the simple kernel has no queue to share; runtime-reloaded modules carry the single-frame kernels
+// only; per-frame powers need the Mandelbulb's N >= 1 kernels.
+static bool batch_shares_launch(const frm_ctx* ctx, const KernelArgs& a, uint32_t count, bool anim) {
+  return !(count == 1 || kernel_for(ctx, a.npix) == kKernelSimple || ctx->reloaded || (anim && a.s.n == 0));
+}
+// Makes `a` (make_args of any of the frames) the shared launch of the `count` frames, frame k written
+// frame_stride_bytes after frame k - 1.
+static void set_batch(const frm_ctx* ctx, KernelArgs& a, uint32_t count, const frm_parameters* params,
+                      const float* powers, bool anim, size_t frame_stride_bytes) {
+  a.batch = count;
+  a.out_stride = (uint32_t)(frame_stride_bytes / 4u);
+  a.anim = anim ? 1u : 0u;
+  memcpy(a.mb_powers, powers, sizeof(float) * count);
+  FrameUniforms fk;
+  for (uint32_t k = 0; k < count; ++k) {
+    compute_frame_uniforms(params[k], ctx->width, ctx->height, ctx->max_steps, &fk);
+    memcpy(a.cams[k].row, fk.row, sizeof(fk.row));
+    a.cams[k].origin = fk.origin;
+  }
+}
+
 int frm_render_bands_batch(frm_ctx* ctx, uint32_t count, const frm_parameters* params, uint8_t* dev_dst,
                            size_t dst_bytes, size_t frame_stride_bytes, uint32_t band_rows, uint32_t first_band,
                            uint32_t band_stride,
@@ -789,31 +839,20 @@ int frm_render_bands_batch(frm_ctx* ctx, uint32_t count, const frm_parameters* p
   if ((uint64_t)rows * ctx->width * count >= 0xFFFFFFFFull - kQueueHeadroom)
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "batch of %u frames of %u x %u local pixels too large", count,
                 ctx->width, rows);
-  // frames of one launch may differ in camera, and for the Mandelbulb in time (its power,
-  // fragment.wgsl:75, is the only time-derived constant): otherwise the same scene uniforms
-  // (scene, iterations, time-derived constants) and aspect
+  // the frames share their scene uniforms (batch_uniforms) and their aspect
   SceneUniforms s0;
-  compute_scene_uniforms(params[0], ctx->flags, &s0);
-  if (int rc = check_parameters(ctx, s0, params[0])) return rc;
   bool anim = false;
   float powers[FRM_MAX_BATCH];
-  powers[0] = s0.mb_power;
-  for (uint32_t k = 1; k < count; ++k) {
-    SceneUniforms sk;
-    compute_scene_uniforms(params[k], ctx->flags, &sk);
-    powers[k] = sk.mb_power;
-    if (is_mandelbulb(s0.family) && sk.family == s0.family && sk.mb_power != s0.mb_power) {
-      anim = true;
-      sk.mb_power = s0.mb_power;
-      sk.mb_power_m1 = s0.mb_power_m1;
-    }
-    if (memcmp(&s0, &sk, sizeof(s0)) != 0 || params[k].aspect_scale[0] != params[0].aspect_scale[0] ||
-        params[k].aspect_scale[1] != params[0].aspect_scale[1])
-      return fail(ctx, FRM_ERR_INVALID_ARGUMENT,
-                  "batch frame %u differs from frame 0 in more than the camera and the Mandelbulb's time "
-                  "(scene, iterations, time-derived constants, aspect)",
-                  k);
-  }
+  uint32_t differs = batch_uniforms(ctx, count, params, &s0, powers, &anim);
+  if (int rc = check_parameters(ctx, s0, params[0])) return rc;
+  for (uint32_t k = 1; k < count && (!differs || k < differs); ++k)
+    if (params[k].aspect_scale[0] != params[0].aspect_scale[0] || params[k].aspect_scale[1] != params[0].aspect_scale[1])
+      differs = k;
+  if (differs)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT,
+                "batch frame %u differs from frame 0 in more than the camera and the Mandelbulb's time "
+                "(scene, iterations, time-derived constants, aspect)",
+                differs);
   FRM_HIP(ctx, hipSetDevice(ctx->device));
   if (int rc = ring_leave(ctx)) return rc;
   ctx->params = params[count - 1];  // the context's parameters: the batch's last frame
@@ -822,10 +861,7 @@ int frm_render_bands_batch(frm_ctx* ctx, uint32_t count, const frm_parameters* p
   hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
   unsigned long long* counters = dev_counters ? (unsigned long long*)dev_counters : ctx->counters;
   KernelArgs a = make_args(ctx, ctx->params, ctx->scene, dev_dst, counters, band_rows, first_band, band_stride, rows);
-  FrameUniforms fk;
-  // one launch per frame: the simple kernel has no queue to share; runtime-reloaded modules carry
-  // the single-frame kernels only; per-frame powers need the Mandelbulb's N >= 1 kernels
-  if (count == 1 || kernel_for(ctx, a.npix) == kKernelSimple || ctx->reloaded || (anim && s0.n == 0)) {
+  if (!batch_shares_launch(ctx, a, count, anim)) {  // one launch per frame
     for (uint32_t k = 0; k < count; ++k) {
       SceneUniforms sk;
       compute_scene_uniforms(params[k], ctx->flags, &sk);
@@ -835,16 +871,142 @@ int frm_render_bands_batch(frm_ctx* ctx, uint32_t count, const frm_parameters* p
     }
     return FRM_OK;
   }
-  a.batch = count;
-  a.out_stride = (uint32_t)(frame_stride_bytes / 4u);
-  a.anim = anim ? 1u : 0u;
-  memcpy(a.mb_powers, powers, sizeof(float) * count);
-  for (uint32_t k = 0; k < count; ++k) {
-    compute_frame_uniforms(params[k], ctx->width, ctx->height, ctx->max_steps, &fk);
-    memcpy(a.cams[k].row, fk.row, sizeof(fk.row));
-    a.cams[k].origin = fk.origin;
-  }
+  set_batch(ctx, a, count, params, powers, anim, frame_stride_bytes);
   return launch(ctx, a, s);
+}
+
+// Sub-frames per chunk of a shutter frame of the context's size (include/frm.h frm_render_shutter):
+// what the context allows (FRM_SHUTTER_CHUNK), 1 GiB of scratch and a shared launch's u32 fetch
+// positions (frm_render_bands_batch), at least 1.
+static uint32_t shutter_chunk(const frm_ctx* ctx, uint32_t count) {
+  const uint64_t npix = (uint64_t)ctx->width * ctx->height;
+  uint64_t n = count < ctx->shutter_chunk ? count : ctx->shutter_chunk;
+  const uint64_t by_bytes = (1ull << 30) / (npix * 4u), by_queue = (0xFFFFFFFFull - kQueueHeadroom - 1u) / npix;
+  if (n > by_bytes) n = by_bytes;
+  if (n > by_queue) n = by_queue;
+  return n ? (uint32_t)n : 1u;
+}
+
+int frm_render_shutter(frm_ctx* ctx, uint32_t count, const frm_parameters* params, frm_stats* stats) {
+  if (!ctx) return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (!params || count == 0 || count > FRM_MAX_SHUTTER_SAMPLES)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "params is NULL or count %u outside [1, %u]", count,
+                FRM_MAX_SHUTTER_SAMPLES);
+  if (ctx->group) return not_on_group(ctx, "frm_render_shutter");
+  if (ctx->adaptive > 1u)
+    return fail(ctx, FRM_ERR_UNSUPPORTED, "frm_render_shutter: not available on an adaptive context (frm_set_adaptive)");
+  if (!ctx->width) return fail(ctx, FRM_ERR_NOT_READY, "frm_resize has not been called");
+  for (uint32_t k = 0; k < count; ++k) {
+    SceneUniforms sk;
+    compute_scene_uniforms(params[k], ctx->flags, &sk);
+    if (int rc = check_parameters(ctx, sk, params[k])) return rc;
+    if (params[k].scene_index != params[0].scene_index || params[k].num_iterations != params[0].num_iterations ||
+        params[k].aspect_scale[0] != params[0].aspect_scale[0] || params[k].aspect_scale[1] != params[0].aspect_scale[1])
+      return fail(ctx, FRM_ERR_INVALID_ARGUMENT,
+                  "sub-frame %u differs from sub-frame 0 in scene_index, num_iterations or aspect_scale", k);
+  }
+  FRM_HIP(ctx, hipSetDevice(ctx->device));
+  int rc = ring_quiesce(ctx);  // a frame outside the ring: the ring's frames first
+  if (rc) return rc;
+  ctx->last_is_ring = false;
+  if (stats && (rc = synchronize_all(ctx))) return rc;  // the counters must hold this frame alone
+  ctx->params = params[count - 1];
+  compute_scene_uniforms(ctx->params, ctx->flags, &ctx->scene);
+  ctx->has_params = true;
+  const uint32_t si = ctx->next_slot;
+  Slot* sl = nullptr;
+  hipStream_t s;
+  if ((rc = begin_frame(ctx, &sl, &s))) return rc;
+  const uint32_t S = ctx->supersample, chunk = shutter_chunk(ctx, count);
+  const size_t sub_bytes = (size_t)ctx->width * ctx->height * 4u, npix_out = (size_t)ctx->out_width * ctx->out_height;
+  const bool carried = chunk < count;  // several chunks: their sums go through the slot's accumulator
+  if ((rc = ensure_shutter(ctx, *sl, chunk * sub_bytes, carried ? npix_out * sizeof(float4) : 0))) return rc;
+  sl->adaptive[sl->fb_idx] = false;
+  uint8_t* frame = sl->fb();  // what shown() reads of the slot
+  if (S > 1u) {
+    if ((rc = ensure_res(ctx, *sl, npix_out * 4u))) return rc;
+    frame = sl->res[sl->fb_idx].p;
+  }
+  float* acc = carried ? (float*)sl->shutter_acc.p : nullptr;
+  if (acc) FRM_HIP(ctx, hipMemsetAsync(acc, 0, npix_out * sizeof(float4), s));
+  if (stats && (rc = stats_begin(ctx, s))) return rc;
+  for (uint32_t first = 0; first < count; first += chunk) {
+    const uint32_t n = count - first < chunk ? count - first : chunk;
+    const frm_parameters* ps = params + first;
+    SceneUniforms s0;
+    float powers[FRM_MAX_BATCH];
+    bool anim = false;
+    const bool same = batch_uniforms(ctx, n, ps, &s0, powers, &anim) == 0;
+    KernelArgs a = make_args(ctx, ps[0], s0, sl->shutter_src.p, ctx->counters, ctx->height, 0, 1, ctx->height);
+    // every launch of the frame runs on its slot (launch() takes the context's next one and moves on)
+    if (same && batch_shares_launch(ctx, a, n, anim)) {
+      set_batch(ctx, a, n, ps, powers, anim, sub_bytes);
+      ctx->next_slot = si;
+      if ((rc = launch(ctx, a, s))) return rc;
+    } else {
+      for (uint32_t k = 0; k < n; ++k) {
+        SceneUniforms sk;
+        compute_scene_uniforms(ps[k], ctx->flags, &sk);
+        a = make_args(ctx, ps[k], sk, sl->shutter_src.p + k * sub_bytes, ctx->counters, ctx->height, 0, 1, ctx->height);
+        ctx->next_slot = si;
+        if ((rc = launch(ctx, a, s))) return rc;
+      }
+    }
+    const bool last = first + n == count;
+    FRM_HIP(ctx, launch_shutter(sl->shutter_src.p, sub_bytes, n, acc, last ? frame : nullptr, ctx->out_width,
+                                ctx->out_height, S, count * S * S, s));
+  }
+  FRM_HIP(ctx, hipEventRecord(sl->done, s));  // covers the accumulation
+  show_slot(ctx, *sl);
+  ctx->shutter_seq = ctx->render_seq;
+  keep_render_params(ctx);
+  if (stats) {
+    uint64_t host[FRM_NUM_COUNTERS];
+    float ms = 0.0f;
+    if ((rc = stats_end(ctx, s, host, &ms)) || (rc = frm_stats_from_counters(ctx, host, stats))) return rc;
+    stats->kernel_ms = ms;
+  }
+  return FRM_OK;
+}
+
+int frm_accumulate(frm_ctx* ctx, const uint8_t* dev_src, size_t src_bytes, size_t frame_stride_bytes, uint32_t count,
+                   uint32_t out_width, uint32_t out_height, uint32_t factor, float* dev_acc, size_t acc_bytes,
+                   uint32_t divisor, uint8_t* dev_dst, size_t dst_bytes, void* stream) {
+  if (!ctx || !dev_src || (!dev_acc && !dev_dst))
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "ctx/dev_src is NULL, or both dev_acc and dev_dst are");
+  if (factor == 0 || factor > FRM_MAX_SUPERSAMPLE || count == 0 || count > FRM_MAX_SHUTTER_SAMPLES)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "factor %u outside [1, %u] or count %u outside [1, %u]", factor,
+                FRM_MAX_SUPERSAMPLE, count, FRM_MAX_SHUTTER_SAMPLES);
+  const uint32_t limit = FRM_MAX_DIMENSION / factor;
+  if (out_width == 0 || out_height == 0 || out_width > limit || out_height > limit)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "output size %ux%u outside [1, %u]^2 (factor %u)", out_width, out_height,
+                limit, factor);
+  if (dev_dst && divisor == 0) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "divisor is 0");
+  const size_t npix = (size_t)out_width * out_height, frame_need = npix * factor * factor * 4u;
+  const uintptr_t sa = reinterpret_cast<uintptr_t>(dev_src), aa = reinterpret_cast<uintptr_t>(dev_acc),
+                  da = reinterpret_cast<uintptr_t>(dev_dst);
+  if (sa % 4u || da % 4u || aa % 16u)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "dev_src / dev_dst not 4-byte aligned or dev_acc not 16-byte aligned");
+  if (frame_stride_bytes % 4u || frame_stride_bytes < frame_need)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "frame stride %zu: below a frame's %zu bytes or not a multiple of 4",
+                frame_stride_bytes, frame_need);
+  if (src_bytes < frame_need || (src_bytes - frame_need) / frame_stride_bytes < count - 1u)
+    return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "src holds %zu bytes, %u frames %zu bytes apart need %zu", src_bytes, count,
+                frame_stride_bytes, (size_t)(count - 1u) * frame_stride_bytes + frame_need);
+  const size_t src_need = (size_t)(count - 1u) * frame_stride_bytes + frame_need;
+  const size_t acc_need = dev_acc ? npix * sizeof(float4) : 0, dst_need = dev_dst ? npix * 4u : 0;
+  if (acc_bytes < acc_need)
+    return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "acc holds %zu bytes, the sums need %zu", acc_bytes, acc_need);
+  if (dst_bytes < dst_need)
+    return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "dst holds %zu bytes, the frame needs %zu", dst_bytes, dst_need);
+  auto overlap = [](uintptr_t a, size_t an, uintptr_t b, size_t bn) { return an && bn && a < b + bn && b < a + an; };
+  if (overlap(sa, src_need, aa, acc_need) || overlap(sa, src_need, da, dst_need) || overlap(aa, acc_need, da, dst_need))
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "dev_src, dev_acc and dev_dst overlap");
+  FRM_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = ring_leave(ctx)) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  FRM_HIP(ctx, launch_shutter(dev_src, frame_stride_bytes, count, dev_acc, dev_dst, out_width, out_height, factor, divisor, s));
+  return FRM_OK;
 }
 
 int frm_unshuffle_bands(frm_ctx* ctx, const uint8_t* dev_src, size_t rank_stride_bytes, uint8_t* dev_dst,
@@ -945,6 +1107,8 @@ int frm_debug_trace(frm_ctx* ctx, float* out, size_t n_floats) {
   if (n_floats < npix * 10u)
     return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "out holds %zu floats, the trace needs %zu", n_floats, npix * 10u);
   const Slot& sl = ctx->slots[ctx->last_slot];
+  if (ctx->render_seq && ctx->shutter_seq == ctx->render_seq && !ctx->last_is_ring)
+    return fail(ctx, FRM_ERR_NOT_READY, "the last frame was a frm_render_shutter frame: no single frame to trace");
   if (!ctx->render_seq || sl.seq != ctx->render_seq)
     return fail(ctx, FRM_ERR_NOT_READY, "no frm_render, or a later launch reused its slot's records");
   if (!sl.records.p || sl.records.cap < npix * kRecordBytes || !sl.sched_whole || sl.sched_w != ctx->width || sl.sched_h != ctx->height)

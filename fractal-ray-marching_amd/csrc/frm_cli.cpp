@@ -9,7 +9,12 @@
 //              [--simple] [--sphere] [--out file.ppm | pattern_%04d.ppm]
 //              [--frames F] [--dt S] [--keys BITS] [--orbit RAD_PER_S]
 //              [--lock-yaw 0..4] [--lock-pitch] [--time-factor X] [--gpus N] [--batch B]
-//              [--ssaa K] [--adaptive S] [--edge-threshold T]
+//              [--ssaa K] [--adaptive S] [--edge-threshold T] [--shutter-samples T] [--shutter F]
+// With --shutter-samples T (1..32, default 1) every frame is motion-blurred: the mean, in linear
+// light, of T sub-frames that step the frame's own state (time, camera) through the fraction F
+// (--shutter, 0 < F <= 1, default 0.5) of --dt (frm_shutter_parameters, frm_render_shutter). The main
+// trajectory advances by dt as without it; the JSON lines count all T sub-frames. Combines with
+// --ssaa; not with --batch, --adaptive or --gpus (the shutter already batches its sub-frames).
 // With --ssaa K (1..4) every frame is rendered with K x K samples per pixel and resolved in linear
 // light (frm_set_supersampling); W x H stay the size of the written frames, the work counters in
 // the JSON lines are those of the (K*W) x (K*H) frame rendered. With --batch the context stays plain
@@ -73,7 +78,7 @@ static int write_ppm(const char* out, uint32_t fr, const uint8_t* rgba, uint32_t
 // the launch's, reported per launch.
 static int render_batched(frm_ctx* ctx, frm_parameters p, frm_camera cam, frm_timing timing, uint32_t keys,
                           float dt, uint32_t frames, uint32_t batch, uint32_t width, uint32_t height,
-                          uint32_t ssaa, uint32_t adaptive, uint32_t edge_threshold, const char* out) {
+                          uint32_t ssaa, uint32_t adaptive, uint32_t edge_threshold, float shutter, const char* out) {
   std::vector<frm_parameters> ps(frames);
   std::vector<frm_camera> cams(frames);
   for (uint32_t fr = 0; fr < frames; ++fr) {
@@ -124,11 +129,12 @@ static int render_batched(frm_ctx* ctx, frm_parameters p, frm_camera cam, frm_ti
       printf("{\"frame\": %u, \"out\": \"%s\", \"width\": %u, \"height\": %u, \"time\": %.6f, "
              "\"pos\": [%.5f, %.5f, %.5f], \"yaw\": %.5f, \"pitch\": %.5f, \"kernel_ms\": %.3f, "
              "\"batch\": %u, \"launch_march_steps\": %llu, \"launch_hit_pixels\": %llu, \"gsteps_per_s\": %.3f, "
-             "\"ssaa\": %u, \"adaptive\": %u, \"edge_threshold\": %u, \"refined_pixels\": %llu}\n",
+             "\"ssaa\": %u, \"adaptive\": %u, \"edge_threshold\": %u, \"refined_pixels\": %llu, "
+             "\"shutter_samples\": 1, \"shutter\": %.6f}\n",
              fr, name, width, height, ps[fr].time, cams[fr].position[0], cams[fr].position[1], cams[fr].position[2],
              cams[fr].yaw, cams[fr].pitch, ms / n, n, (unsigned long long)(c[2] + c[3]), (unsigned long long)c[1],
              (double)(c[2] + c[3]) / (ms * 1e-3) / 1e9, ssaa, adaptive, edge_threshold,
-             (unsigned long long)(rc[(size_t)b * FRM_NUM_COUNTERS] / (adaptive * adaptive)));
+             (unsigned long long)(rc[(size_t)b * FRM_NUM_COUNTERS] / (adaptive * adaptive)), shutter);
     }
   }
   (void)hipFree(dev);
@@ -152,6 +158,8 @@ int main(int argc, char** argv) {
   uint32_t ssaa = 1;   // samples per pixel and axis
   uint32_t adaptive = 1, edge_threshold = FRM_ADAPTIVE_DEFAULT_THRESHOLD;  // --adaptive, --edge-threshold
   bool ssaa_given = false, adaptive_given = false;
+  uint32_t shutter_samples = 1;  // sub-frames per frame
+  float shutter = 0.5f;          // the fraction of dt they span
   for (int i = 1; i < argc; ++i) {
     const char* a = argv[i];
     auto next = [&](void) -> const char* {
@@ -204,10 +212,34 @@ int main(int argc, char** argv) {
       (thr ? edge_threshold : adaptive) = (uint32_t)k;
       adaptive_given = true;
     }
+    else if (!strcmp(a, "--shutter-samples")) {
+      const char* v = next();
+      char* end = nullptr;
+      const long k = strtol(v, &end, 10);
+      if (end == v || *end || k < 1 || k > (long)FRM_MAX_SHUTTER_SAMPLES) {
+        fprintf(stderr, "frm_render: --shutter-samples %s outside [1, %u]\n", v, FRM_MAX_SHUTTER_SAMPLES);
+        return 2;
+      }
+      shutter_samples = (uint32_t)k;
+    }
+    else if (!strcmp(a, "--shutter")) {
+      const char* v = next();
+      char* end = nullptr;
+      shutter = strtof(v, &end);
+      if (end == v || *end || !(shutter > 0.0f && shutter <= 1.0f)) {
+        fprintf(stderr, "frm_render: --shutter %s outside (0, 1]\n", v);
+        return 2;
+      }
+    }
     else { fprintf(stderr, "unknown argument %s\n", a); return 2; }
   }
   if (ssaa_given && adaptive_given) {
     fprintf(stderr, "frm_render: --adaptive / --edge-threshold and --ssaa exclude each other\n");
+    return 2;
+  }
+  if (shutter_samples > 1 && (batch > 1 || adaptive > 1 || gpus > 0)) {
+    fprintf(stderr, "frm_render: --shutter-samples excludes --batch, --adaptive and --gpus (frm_render_shutter batches "
+                    "its sub-frames on one plain or supersampled context)\n");
     return 2;
   }
   frm_ctx* ctx = nullptr;
@@ -259,7 +291,8 @@ int main(int argc, char** argv) {
     return 2;
   }
   if (batch > 1) return render_batched(ctx, p, cam, timing, keys, dt, frames, batch, width, height, ssaa, adaptive,
-                                   edge_threshold, out);
+                                   edge_threshold, shutter, out);
+  std::vector<frm_parameters> sub(shutter_samples);
   for (uint32_t fr = 0; fr < frames; ++fr) {
     if (fr > 0) {  // initialized_app.rs:43-48, with a fixed frame time
       const float delta = frm_timing_update(&timing, &p, dt);
@@ -268,8 +301,13 @@ int main(int argc, char** argv) {
     }
     frm_stats st;
     memset(&st, 0, sizeof(st));
-    check(frm_set_parameters(ctx, &p), ctx, "frm_set_parameters");
-    check(frm_render(ctx, &st), ctx, "frm_render");  // a group: render, gather and reassembly
+    if (shutter_samples > 1) {  // the frame's own state stepped through the shutter interval
+      frm_shutter_parameters(&p, &cam, &timing, keys, dt, shutter_samples, shutter, sub.data());
+      check(frm_render_shutter(ctx, shutter_samples, sub.data(), &st), ctx, "frm_render_shutter");
+    } else {
+      check(frm_set_parameters(ctx, &p), ctx, "frm_set_parameters");
+      check(frm_render(ctx, &st), ctx, "frm_render");  // a group: render, gather and reassembly
+    }
     check(frm_read_frame(ctx, rgba.data(), rgba.size()), ctx, "frm_read_frame");
     char name[4096];
     if (strchr(out, '%')) snprintf(name, sizeof(name), out, fr);
@@ -282,11 +320,13 @@ int main(int argc, char** argv) {
     printf("{\"frame\": %u, \"out\": \"%s\", \"width\": %u, \"height\": %u, \"time\": %.6f, "
            "\"pos\": [%.5f, %.5f, %.5f], \"yaw\": %.5f, \"pitch\": %.5f, \"kernel_ms\": %.3f, "
            "\"march_steps\": %llu, \"hit_pixels\": %llu, \"gsteps_per_s\": %.3f, \"ssaa\": %u, "
-           "\"adaptive\": %u, \"edge_threshold\": %u, \"refined_pixels\": %llu}\n",
+           "\"adaptive\": %u, \"edge_threshold\": %u, \"refined_pixels\": %llu, \"shutter_samples\": %u, "
+           "\"shutter\": %.6f}\n",
            fr, name, width, height, p.time, cam.position[0], cam.position[1], cam.position[2], cam.yaw,
            cam.pitch, st.kernel_ms, (unsigned long long)st.march_steps, (unsigned long long)st.hit_pixels,
            st.march_steps / (st.kernel_ms * 1e-3) / 1e9, ssaa, adaptive, edge_threshold,
-           (unsigned long long)(adaptive > 1 ? (st.pixels - (uint64_t)width * height) / (adaptive * adaptive) : 0));
+           (unsigned long long)(adaptive > 1 ? (st.pixels - (uint64_t)width * height) / (adaptive * adaptive) : 0),
+           shutter_samples, shutter);
   }
   frm_destroy(ctx);
   return 0;

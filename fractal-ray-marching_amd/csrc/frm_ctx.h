@@ -86,6 +86,9 @@ struct Slot {
   PoolBuf refine_list;
   uint32_t* refine_ctl = nullptr;
   uint32_t refine_w = 0, refine_h = 0;  // the frame the list belongs to
+  // motion blur (frm_render_shutter): the sub-frames of one chunk, back to back, and the f32 sums a
+  // frame of several chunks carries between them (a float4 per output pixel)
+  PoolBuf shutter_src, shutter_acc;
   unsigned int* queue = nullptr;
   PoolBuf records;  // persistent kernel scratch (ShadeGeom[n] then ShadeTail[n], record_tails), grown on demand
   // pixel scheduling state (frm_sched.hip), sched_cap entries each: 0..cap-1, the fetch
@@ -239,6 +242,8 @@ struct frm_ctx {
   frm_parameters params{};
   bool has_params = false;
   SceneUniforms scene{};
+  uint32_t shutter_chunk = FRM_MAX_SHUTTER_SAMPLES;  // frm_render_shutter: sub-frames per chunk at most (FRM_SHUTTER_CHUNK)
+  uint64_t shutter_seq = 0;  // render_seq of the last frm_render_shutter (0: none)
   Ring ring;
   bool ring_enabled = false;  // FRM_RING=1: the resident frame ring (opt-in: slower)
   bool last_is_ring = false; // the last frm_render posted a ring frame (ring.last_seq)
@@ -276,6 +281,7 @@ int ensure_fb(frm_ctx* ctx, Slot& sl, size_t bytes);
 int select_fb(frm_ctx* ctx, Slot& sl, uint32_t i);
 int ensure_res(frm_ctx* ctx, Slot& sl, size_t bytes);
 int resolve_frame(frm_ctx* ctx, Slot& sl);
+int ensure_shutter(frm_ctx* ctx, Slot& sl, size_t src_bytes, size_t acc_bytes);
 const uint8_t* shown(const frm_ctx* ctx, const Slot& sl);
 uint32_t band_local_rows(uint32_t height, uint32_t band_rows, uint32_t first, uint32_t stride);
 uint32_t group_band_rows(uint32_t height, uint32_t n);

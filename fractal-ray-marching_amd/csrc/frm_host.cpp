@@ -356,3 +356,21 @@ extern "C" void frm_timing_update_time_factor(frm_timing* t, float delta) {
 extern "C" void frm_timing_stop_time(frm_timing* t) {
   if (t) t->time_factor = 0.0f;
 }
+
+// ---- motion blur: the sub-frames of one shutter interval (include/frm.h) ------------------------
+extern "C" void frm_shutter_parameters(const frm_parameters* p, const frm_camera* c, const frm_timing* t,
+                                       uint32_t held_keys, float dt, uint32_t samples, float shutter,
+                                       frm_parameters* out) {
+  if (!p || !c || !t || !out || samples == 0) return;
+  frm_parameters p2 = *p;
+  frm_camera c2 = *c;
+  frm_timing t2 = *t;
+  out[0] = p2;
+  for (uint32_t s = 1; s < samples; ++s) {
+    const float h = shutter * dt / (float)samples;
+    const float delta = frm_timing_update(&t2, &p2, h);
+    frm_camera_update(&c2, held_keys, delta);
+    frm_parameters_update_camera_from(&p2, &c2);
+    out[s] = p2;
+  }
+}

@@ -249,6 +249,13 @@ hipError_t launch_unshuffle(const uint8_t* src, size_t rank_stride, uint8_t* dst
 // with alpha 255).
 hipError_t launch_resolve(const uint8_t* src, uint8_t* dst, uint32_t dw, uint32_t dh, uint32_t factor,
                           hipStream_t stream);
+// Motion blur (frm_render_shutter, frm_accumulate; frm_shutter_kernels.h): the sum, in linear light,
+// of the factor x factor texels under each output pixel over `count` (>= 1) sub-frames
+// frame_stride_bytes (a multiple of 4) apart in src, each factor*dh rows of factor*dw RGBA8 sRGB
+// texels, 4-byte aligned. acc: nullptr, or dw*dh float4 (16-byte aligned) the sum starts from and
+// is stored back to; dst: nullptr, or dh rows of dw texels that receive encode(sum / divisor).
+hipError_t launch_shutter(const uint8_t* src, size_t frame_stride_bytes, uint32_t count, float* acc, uint8_t* dst,
+                          uint32_t dw, uint32_t dh, uint32_t factor, uint32_t divisor, hipStream_t stream);
 // Adaptive supersampling (frm_set_adaptive, frm_refine; frm_refine_kernels.h): dst = src with alpha
 // 255 (height rows of width RGBA8 sRGB texels, both 4-byte aligned, not overlapping), except the
 // pixels whose 3 x 3 neighbourhood in src has a contrast >= threshold: those are the box resolve

@@ -11,6 +11,7 @@
 
 #include "frm_render_kernels.h"
 #include "frm_refine_kernels.h"
+#include "frm_shutter_kernels.h"
 
 namespace frm {
 

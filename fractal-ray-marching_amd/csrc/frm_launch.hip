@@ -58,6 +58,12 @@ static int ensure_refine(frm_ctx* ctx, Slot& sl, size_t npix) {
     if (int rc = dev_alloc(ctx, (void**)&sl.refine_ctl, kRefineCtlBytes, sl.stream)) return rc;
   return pool_grow(ctx, sl.refine_list, npix * sizeof(uint32_t), sl.stream);
 }
+// The slot's motion-blur scratch for chunks of src_bytes of sub-frames and, for a frame of several
+// chunks, acc_bytes of sums (0: none), grown on the slot stream (the slot's last shutter frame ran there).
+int ensure_shutter(frm_ctx* ctx, Slot& sl, size_t src_bytes, size_t acc_bytes) {
+  if (int rc = pool_grow(ctx, sl.shutter_src, src_bytes, sl.stream)) return rc;
+  return pool_grow(ctx, sl.shutter_acc, acc_bytes, sl.stream);
+}
 // The second image of the slot's current framebuffer, on the slot stream, after the frame is
 // complete there: the box resolve of a supersampled context, or the adaptive frame of an adaptive
 // one (the edge pass over the frame, then the samples of its refined pixels; their work is added

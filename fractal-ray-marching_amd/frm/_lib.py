@@ -25,6 +25,7 @@ FRM_NUM_SCENES = 19
 FRM_MAX_FRAMES_IN_FLIGHT = 8
 FRM_MAX_DEVICES = 16
 FRM_MAX_BATCH = 32
+FRM_MAX_SHUTTER_SAMPLES = 32
 FRM_MAX_SUPERSAMPLE = 4
 FRM_ADAPTIVE_DEFAULT_THRESHOLD = 16
 FRM_DEFAULT_MAX_STEPS = 5000
@@ -151,6 +152,11 @@ SIGNATURES = [
     ("frm_render_bands_batch", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32,
       ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
+    ("frm_render_shutter", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, _P(FrmStats)]),
+    ("frm_accumulate", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,
+      ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p,
+      ctypes.c_size_t, ctypes.c_void_p]),
     ("frm_unshuffle_bands", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
       ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]),
@@ -184,6 +190,9 @@ SIGNATURES = [
     ("frm_timing_update", ctypes.c_float, [_P(FrmTiming), _P(FrmParameters), ctypes.c_float]),
     ("frm_timing_update_time_factor", None, [_P(FrmTiming), ctypes.c_float]),
     ("frm_timing_stop_time", None, [_P(FrmTiming)]),
+    ("frm_shutter_parameters", None,
+     [_P(FrmParameters), _P(FrmCamera), _P(FrmTiming), ctypes.c_uint32, ctypes.c_float, ctypes.c_uint32,
+      ctypes.c_float, ctypes.c_void_p]),
 ]
 
 _lib = None

@@ -208,3 +208,17 @@ class Timing:
     # timing.rs:36-38
     def stop_time(self):
         _lib.load().frm_timing_stop_time(ctypes.byref(self.raw))
+
+
+def shutter_parameters(parameters, camera, timing, held_keys, dt, samples, shutter):
+    """frm_shutter_parameters: the `samples` sub-frames (a list of Parameters) of one motion-blurred
+    frame whose state is (parameters, camera, timing): the first is `parameters`, each further one
+    steps a private copy of the state by shutter * dt / samples. The inputs are not modified."""
+    samples = int(samples)
+    if samples < 1:
+        raise ValueError("samples must be at least 1")
+    out = (_lib.FrmParameters * samples)()
+    _lib.load().frm_shutter_parameters(ctypes.byref(parameters.raw), ctypes.byref(camera.raw),
+                                       ctypes.byref(timing.raw), int(held_keys), float(dt), samples, float(shutter),
+                                       ctypes.addressof(out))
+    return [Parameters.from_bytes(ctypes.string_at(ctypes.addressof(out[k]), 96)) for k in range(samples)]

@@ -139,6 +139,30 @@ class Renderer:
         self._check(self._lib.frm_render(self.ctx, ctypes.byref(st)))
         return st.as_dict()
 
+    def render_shutter(self, params_list, stats=True):
+        """frm_render_shutter: one motion-blurred frame, the mean in linear light of the sub-frames
+        rendered with params_list (1..FRM_MAX_SHUTTER_SAMPLES Parameters of one scene, e.g. from
+        frm.shutter_parameters); the context's parameters become the last. Returns frm_stats summed
+        over the sub-frames as a dict when stats=True."""
+        arr = (_lib.FrmParameters * max(1, len(params_list)))()
+        for k, p in enumerate(params_list):
+            ctypes.memmove(ctypes.addressof(arr[k]), p.to_bytes(), ctypes.sizeof(_lib.FrmParameters))
+        st = _lib.FrmStats() if stats else None
+        self._check(self._lib.frm_render_shutter(self.ctx, len(params_list), ctypes.addressof(arr),
+                                                 ctypes.byref(st) if stats else None))
+        return st.as_dict() if stats else None
+
+    def accumulate(self, src_ptr, src_bytes, frame_stride, count, out_w, out_h, factor, acc_ptr=0, acc_bytes=0,
+                   divisor=1, dst_ptr=0, dst_bytes=0, stream=0):
+        """frm_accumulate: adds, in linear light, the factor x factor texels under each of the out_h x
+        out_w output pixels over `count` RGBA8 sRGB frames frame_stride bytes apart at device pointer
+        src_ptr, asynchronously on `stream` (0: the context's). acc_ptr (0: none): 16 bytes of f32 sums
+        per output pixel the sum starts from and is stored to; dst_ptr (0: none) receives the frame of
+        sum / divisor."""
+        self._check(self._lib.frm_accumulate(self.ctx, src_ptr, src_bytes, frame_stride, count, out_w, out_h, factor,
+                                             acc_ptr or None, acc_bytes, divisor, dst_ptr or None, dst_bytes,
+                                             stream or None))
+
     def read_frame(self):
         buf = np.empty((self.height, self.width, 4), dtype=np.uint8)
         self._check(self._lib.frm_read_frame(self.ctx, buf.ctypes.data, buf.nbytes))

@@ -381,6 +381,53 @@ int frm_render_bands_batch(frm_ctx* ctx, uint32_t count, const frm_parameters* p
                            uint8_t* dev_dst, size_t dst_bytes, size_t frame_stride_bytes, uint32_t band_rows,
                            uint32_t first_band, uint32_t band_stride, void* stream,
                            uint64_t* dev_counters);
+/* ---- motion blur: one frame as the mean, in linear light, of `count` sub-frames sampled over a
+ *      shutter interval (no reference counterpart: the reference renders instantaneous poses). With
+ *      S the context's supersampling factor, sub-frame k the (S*width) x (S*height) frame frm_render
+ *      would render with params[k], and D the sRGB decode table of the blit, output pixel (X, Y) is,
+ *      for each of R, G, B:
+ *          sum = 0.0f
+ *          for k in 0..count-1, j in 0..S-1, i in 0..S-1:      (sub-frames in the order given, source
+ *            sum = sum + D[frame[k][S*Y+j][S*X+i]]               rows top to bottom, texels left to right)
+ *          code = encode(sum / (float)(count*S*S))              (f32 adds in exactly this order, one
+ *                                                                correctly rounded division, the sRGB store)
+ *      alpha 255. One sum over all count*S*S samples: not a resolve per sub-frame and a mean of
+ *      codes. count = 1 gives frm_render's bytes; identical sub-frames give the plain frame.
+ * frm_render_shutter: frm_render for one such frame. It takes one render slot and its stream as
+ *      frm_render does (frames in flight, tickets, stats == NULL being asynchronous, frm_resize
+ *      without a drain: all as there), and frm_read_frame, frm_present, their async forms and
+ *      frm_frame_pixels see the blurred frame. Every params[k] is checked as frm_set_parameters
+ *      checks it; all must share scene_index, num_iterations and aspect_scale
+ *      (FRM_ERR_INVALID_ARGUMENT otherwise); time and camera may differ in every scene. The
+ *      context's parameters become params[count-1]. Where frm_render_bands_batch's rules allow it
+ *      (the same scene uniforms up to the Mandelbulb's power, the persistent kernel, no reloaded
+ *      module) the sub-frames share one persistent launch, else each gets its own, with the same
+ *      bytes. The sub-frames are rendered into a scratch of the slot in chunks (at most
+ *      FRM_MAX_SHUTTER_SAMPLES, 1 GiB of scratch, and the environment variable FRM_SHUTTER_CHUNK
+ *      read by frm_create, a tuning knob); each chunk is added to an f32 accumulator and the last
+ *      one writes the frame, with the bytes of a single chunk. frm_stats is the sum over the
+ *      sub-frames (pixels = count * S*S * width * height); kernel_ms includes the accumulation.
+ *      FRM_ERR_UNSUPPORTED on a group or an adaptive context, FRM_ERR_NOT_READY before frm_resize,
+ *      FRM_ERR_INVALID_ARGUMENT for NULL or a count outside 1..FRM_MAX_SHUTTER_SAMPLES; a refusal
+ *      changes nothing. Shutter frames never go through the resident ring, and frm_debug_trace after
+ *      one gives FRM_ERR_NOT_READY (there is no single frame to trace).
+ * frm_accumulate: the accumulation alone, on any context, asynchronous on `stream` (NULL: the
+ *      context's). dev_src holds `count` (1..FRM_MAX_SHUTTER_SAMPLES) frames frame_stride_bytes
+ *      apart (a multiple of 4, at least a frame's bytes), each factor*out_height rows of
+ *      factor*out_width RGBA8 sRGB texels; factor 1..FRM_MAX_SUPERSAMPLE and factor x each size
+ *      at most FRM_MAX_DIMENSION. dev_acc: NULL, or 16 bytes per output pixel (float x, y, z: the
+ *      sums of R, G, B; w is written as 0), 16-byte aligned, read AND written: the sum starts from
+ *      it, so the caller zeroes it before the first chunk (all-zero bytes are 0.0f). dev_dst: NULL,
+ *      or out_height rows of out_width texels that receive the frame of sum / divisor (divisor >= 1:
+ *      the number of samples summed so far). Both NULL, misaligned or overlapping buffers and
+ *      sizes out of range are FRM_ERR_INVALID_ARGUMENT, a short buffer FRM_ERR_BUFFER_TOO_SMALL.
+ *      The source alpha is ignored. Additive: FRM_ABI_VERSION stays 5. */
+#define FRM_MAX_SHUTTER_SAMPLES 32u   /* = FRM_MAX_BATCH */
+int frm_render_shutter(frm_ctx* ctx, uint32_t count, const frm_parameters* params, frm_stats* stats);
+int frm_accumulate(frm_ctx* ctx, const uint8_t* dev_src, size_t src_bytes, size_t frame_stride_bytes,
+                   uint32_t count, uint32_t out_width, uint32_t out_height, uint32_t factor,
+                   float* dev_acc, size_t acc_bytes, uint32_t divisor,
+                   uint8_t* dev_dst, size_t dst_bytes, void* stream);
 /* Reassemble a frame from per-rank band buffers laid out rank-major in dev_src
  * (rank r's buffer starts at r*rank_stride_bytes, as written by frm_render_bands with
  * first_band = r, band_stride = ranks) into row-major dev_dst. Asynchronous. */
@@ -510,6 +557,16 @@ void frm_timing_init(frm_timing* t);                                     /* timi
 float frm_timing_update(frm_timing* t, frm_parameters* p, float delta_seconds);
 void frm_timing_update_time_factor(frm_timing* t, float delta);          /* timing.rs:32-34 */
 void frm_timing_stop_time(frm_timing* t);                                /* timing.rs:36-38 */
+
+/* The sub-frames of one motion-blurred frame (frm_render_shutter) of a scripted fly-through, as
+ * the CLI samples them: `samples` parameter sets that step the frame's state through the fraction
+ * `shutter` of its frame time dt. out[0] = *p; for s >= 1, on private copies of p, c and t carried
+ * on from s - 1: h = shutter * dt / (float)samples (f32, in this order);
+ * delta = frm_timing_update(&t, &p, h); frm_camera_update(&c, held_keys, delta);
+ * frm_parameters_update_camera_from(&p, &c); out[s] = p. The inputs are not modified. */
+void frm_shutter_parameters(const frm_parameters* p, const frm_camera* c, const frm_timing* t,
+                            uint32_t held_keys, float dt, uint32_t samples, float shutter,
+                            frm_parameters* out /* samples entries */);
 
 #ifdef __cplusplus
 }
