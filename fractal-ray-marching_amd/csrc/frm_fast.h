@@ -175,8 +175,9 @@ __device__ __forceinline__ float acos_dev(float t) {
   return fma_(r, sg, fma_(sg, -0.5f * kPi, 0.5f * kPi));
 }
 
-// atan2_ for tame x, y (each 0 or with magnitude in [2^-60, 2^40]).
-__device__ __forceinline__ float atan2_tame(float y, float x) {
+// atan2_ for tame x, y (each 0 or with magnitude in [2^-60, 2^40]); NZ: atan2_tame_nz below.
+template <bool NZ>
+__device__ __forceinline__ float atan2_tame_(float y, float x) {
   float ax = fabsf(x), ay = fabsf(y);
   // mx = max_(ax, ay, 2^-100), mn = min_(ax, ay) for finite x, y: plain v_max3 / v_min with
   // |.| source modifiers, without the NaN-quieting canonicalizes the compiler adds to
@@ -192,8 +193,8 @@ __device__ __forceinline__ float atan2_tame(float y, float x) {
   // the octant fix-ups without compares: (c ? h - r : r) == fma(r, c ? -1 : 1, c ? h : 0), one
   // rounding either way (r >= +0); the +-1 is a bit-field insert of c's sign bit into 1.0.
   // c = sign bit of ax - ay (exact difference: negative iff ay > ax, +0 when equal) and of
-  // x + 0 (-0 + 0 = +0: negative iff x < 0).
-  const uint32_t c1 = __float_as_uint(ax - ay), c2 = __float_as_uint(x + 0.0f);
+  // x + 0 (-0 + 0 = +0: negative iff x < 0; NZ: of x itself).
+  const uint32_t c1 = __float_as_uint(ax - ay), c2 = __float_as_uint(NZ ? x : x + 0.0f);
   const float s1 = __uint_as_float(bfi_(0x80000000u, c1, 0x3f800000u));
   const float s2 = __uint_as_float(bfi_(0x80000000u, c2, 0x3f800000u));
   // offsets (c ? h : 0) as fma(s, -h/2, h/2): exact (+0 or h)
@@ -201,6 +202,14 @@ __device__ __forceinline__ float atan2_tame(float y, float x) {
   r = fma_(r, s2, fma_(s2, -0.5f * kPi, 0.5f * kPi));
   return copysignf(r, y);
 }
+__device__ __forceinline__ float atan2_tame(float y, float x) { return atan2_tame_<false>(y, x); }
+
+// atan2_tame for x and y that are both non-zero: each magnitude in [2^-60, 2^40] (the Mandelbulb
+// body's operands once mb_tame() has admitted the wave: it sends zero components to the exact
+// body). The sign of x is then x's own sign bit: no -0 to turn into +0 first, one add less. The
+// rest is atan2_tame's, operation for operation (the 2^-100 floor of mx never applies here).
+// mb_body_tame takes it with -DFRM_ATAN2_NZ=1 only: the headline measured slower with it.
+__device__ __forceinline__ float atan2_tame_nz(float y, float x) { return atan2_tame_<true>(y, x); }
 
 // log_split_ for positive normal finite x by integer arithmetic (the musl logf split):
 // ix = bits(x) - bits(sqrt(1/2)); k = ix >> 23 (arithmetic) is the exponent for a mantissa

@@ -77,6 +77,7 @@ __global__ __launch_bounds__(256) void eval_math(int fn, const float* a, const f
     case 23: r = normalize_wave(mk(x, y, y)).y; break;
     case 24: r = normalize(mk(x, y, y)).x; break;
     case 25: r = normalize(mk(x, y, y)).y; break;
+    case 26: r = atan2_tame_nz(x, y); break;
     default: r = (float)encode_srgb(x, kSrgbThresholds); break;
 #else
     default: r = x; break;

@@ -685,6 +685,29 @@ __device__ unsigned long long g_wave_debug[16u * kWaveDebugSlots];
 #ifndef FRM_HOT_SGPRS
 #define FRM_HOT_SGPRS 0  // 1: max_steps and service_min pinned to SGPRs of their own (slower)
 #endif
+#ifndef FRM_COUNT_DOWN
+#define FRM_COUNT_DOWN 1  // 0: the body loop counts its bodies up and compares twice (A/B builds)
+#endif
+
+// The Mandelbulb body loop's counter (FRM_COUNT_DOWN): the bodies a lane's DE has left before its
+// count exit, N where the DE starts. One subtract-with-borrow per iteration takes 1 from every lane
+// of `pending` (the borrow-in is that wave-uniform mask: other lanes subtract 0) and returns the
+// borrow-out, the pending lanes that went below 0: their body of this iteration is body N + 1,
+// the count exit. It stands for the increment and the two compares of a count upwards, and the
+// exit mask never passes through a VGPR. The DE's bodies so far are n_iter - left (mod 2^32:
+// N + 1 after the count exit, where left is 0xffffffff).
+__device__ __forceinline__ uint64_t count_down(uint32_t& left, uint64_t pending) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  uint64_t out;
+  asm("v_subb_co_u32_e64 %0, %1, %0, 0, %2" : "+v"(left), "=s"(out) : "s"(pending));
+  return out;
+#else  // hipcc's host pass (never run: kernels are device code)
+  const uint64_t bit = 1ull << (threadIdx.x & 63u);
+  const bool in = (pending & bit) != 0, out = in && left == 0u;
+  left -= in ? 1u : 0u;
+  return out ? bit : 0ull;
+#endif
+}
 
 // One work counter of a wave, exactly 64 bits wide. The loops add to its low word, one SGPR; the
 // carry is a wave-uniform branch to a cold block that bumps the high word, which nothing else
@@ -773,6 +796,7 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
   // The lean service pass (below): the Mandelbulb launches (single, MULTI, ANIM, hardware math).
   // Not the ring grid (its register budget is fragile), nor the fixed-trip families.
   constexpr bool kLeanPass = FRM_LEAN_PASS && kMb && !RES;
+  constexpr bool kCountDown = FRM_COUNT_DOWN && kMb;  // count_down() above; else `body` counts up
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
   const uint64_t lane_bit = 1ull << lane;
   constexpr bool multi = MULTI;
@@ -846,6 +870,7 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
   v3 o = mk(0.f, 0.f, 0.f), d = o, nsum = o, q = o, z = o;
   float t = 0.f, closeness = 0.f, dr = 1.f, mag = 0.f, de = 0.f;
   uint32_t it = 0, psteps = 0, body = 0;
+  [[maybe_unused]] uint32_t left = 0;  // kCountDown: in place of `body`
   uint32_t pix_cost = 0;  // the lane's pixel's Mandelbulb bodies (other families: DEs) so far, for
                           // its scheduling key; the wave's body total is counted in SGPRs
 #ifdef FRM_STAMPS
@@ -883,6 +908,9 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
 #ifdef FRM_STAMPS
         n_loop++;
 #endif
+        // kCountDown: by every lane, in front of the branch (the borrow-in selects the lanes)
+        [[maybe_unused]] uint64_t cnt_exit = 0;
+        if constexpr (kCountDown) cnt_exit = count_down(left, pending);
         if (lane_in(pending)) {
 #if defined(FRM_COUNT_EXACT) && defined(__HIP_DEVICE_COMPILE__)  // diagnostic: body-loop iterations, and those that ran the exact body
           n_dbg_total++;
@@ -892,13 +920,21 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
             mb_step<kHw>(lane_power, lane_power - 1.0f, q, mag, z, dr);  // = the host's mb_power_m1
           else
             mb_step<kHw>(su, q, mag, z, dr);
-          body++;
           // N+1 bodies: the distance uses the last loop-top magnitude
-          if (body <= n_iter) mag = mb_length<kHw>(z);
+          if constexpr (kCountDown) {
+            if (!lane_in(cnt_exit)) mag = mb_length<kHw>(z);
+          } else {
+            body++;
+            if (body <= n_iter) mag = mb_length<kHw>(z);
+          }
         }
         // the lanes whose DE ends, tested by every lane outside the body's branch (other lanes'
         // bits fall outside `pending`): a flag set inside it reached the mask through a VGPR
-        pending &= ~(ballot(body > n_iter) | ballot(mag > su.mb_bailout));
+        // (kCountDown: the count exits are a mask already)
+        if constexpr (kCountDown)
+          pending &= ~(cnt_exit | ballot(mag > su.mb_bailout));
+        else
+          pending &= ~(ballot(body > n_iter) | ballot(mag > su.mb_bailout));
       }
       done = !lane_in(pending);  // idle lanes: masked by cons
       live_m = live;
@@ -933,6 +969,7 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
         (void)plain_log;
         de = mb_distance(mag, dr);
 #endif
+        if constexpr (kCountDown) body = n_iter - left;  // wraps to N+1 on a count exit
         pix_cost += body;          // bodies this DE ran (N+1 on a count exit)
         ev_bail = body <= n_iter;  // exit by bailout (incl. before the first body)
         FRM_SUB_END(0);
@@ -1221,7 +1258,10 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
       if constexpr (kMb) {
         z = q;
         dr = 1.f;
-        body = 0;
+        if constexpr (kCountDown)
+          left = n_iter;
+        else
+          body = 0;
         mag = mb_length<kHw>(q);
         done = mag > su.mb_bailout;
       } else {

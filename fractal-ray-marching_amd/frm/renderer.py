@@ -279,7 +279,9 @@ class Renderer:
                # the division ended by v_div_fixup (frm_fast.h div_fix) and the last tap's normalize
                # of (a, b, b), guarded (normalize_wave) and plain
                "div_fix": 21, "normalize_guarded_x": 22, "normalize_guarded_y": 23,
-               "normalize_x": 24, "normalize_y": 25}
+               "normalize_x": 24, "normalize_y": 25,
+               # atan2_tame for two non-zero operands (frm_fast.h atan2_tame_nz)
+               "atan2_tame_nz": 26}
 
     def eval_scene(self, points):
         pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
