@@ -43,6 +43,13 @@ int not_adaptive(frm_ctx* ctx, const char* what) {
               what);
 }
 
+int not_panorama(frm_ctx* ctx, const char* what) {
+  return fail(ctx, FRM_ERR_UNSUPPORTED,
+              "%s: not available on a panorama context (frm_set_panorama); render the faces "
+              "(frm_panorama_parameters) on a plain context and call frm_project_equirect",
+              what);
+}
+
 // The fractal loop work a frame's parameters ask for (include/frm.h FRM_MAX_NUM_ITERATIONS):
 // trips of the DE's loop per evaluation, after the reference's own loop semantics
 // (Sierpinski's i32 loop runs none for N >= 2^31: compute_scene_uniforms sets n = 0).
@@ -238,7 +245,7 @@ int frm_destroy(frm_ctx* ctx) {
     // pool blocks back to the pool (every stream is idle), then the pool itself below
     if (ctx->stream) {
       for (const PoolBuf* b : {&sl.fbs[0], &sl.fbs[1], &sl.res[0], &sl.res[1], &sl.refine_list, &sl.records, &sl.present_dev,
-                               &sl.shutter_src, &sl.shutter_acc})
+                               &sl.shutter_src, &sl.shutter_acc, &sl.pano_src, &sl.pano_tables})
         if (b->p) (void)hipFreeAsync(b->p, ctx->stream);
       for (void* b : {(void*)sl.refine_ctl, (void*)sl.sched_iota, (void*)sl.sched_order, (void*)sl.sched_keys, sl.sched_temp})
         if (b) (void)hipFreeAsync(b, ctx->stream);
@@ -252,6 +259,7 @@ int frm_destroy(frm_ctx* ctx) {
     if (sl.copy_stream) (void)hipStreamDestroy(sl.copy_stream);
   }
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+  release_host_blocks(ctx, true);
   if (ctx->pool) (void)hipMemPoolDestroy(ctx->pool);
   if (ctx->present_buf) (void)hipFree(ctx->present_buf);
   unload_reloaded(ctx->reloaded);
@@ -315,8 +323,32 @@ static int apply_size(frm_ctx* ctx, uint32_t width, uint32_t height, uint32_t fa
   return FRM_OK;
 }
 
+// An output size and a panorama face size N >= 1 (checked by the callers): the render size is that
+// of a face with its guard band, (N + 2)^2. The framebuffer that frm_read_frame sees before the
+// next frm_render holds the larger of a face and the panorama (shown() hands it out at the output
+// size; begin_frame and render_panorama grow the others).
+static int apply_panorama(frm_ctx* ctx, uint32_t width, uint32_t height, uint32_t face_size) {
+  const uint32_t m = face_size + 2u;
+  int rc = resize_render(ctx, m, m);
+  if (rc) return rc;
+  ctx->panorama = face_size;
+  ctx->out_width = width;
+  ctx->out_height = height;
+  Slot& sl = ctx->slots[ctx->last_slot];
+  const size_t face = (size_t)m * m * 4u, out = (size_t)width * height * 4u;
+  if ((rc = select_fb(ctx, sl, sl.fb_idx)) || (rc = ensure_fb(ctx, sl, face > out ? face : out))) return rc;
+  ctx->render_seq = 0;  // no panorama of this shape yet
+  return FRM_OK;
+}
+
 int frm_resize(frm_ctx* ctx, uint32_t width, uint32_t height) {
   if (!ctx) return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (ctx->panorama) {  // the output size is free of the render size
+    if (width == 0 || height == 0 || width > FRM_MAX_DIMENSION || height > FRM_MAX_DIMENSION)
+      return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "panorama size %ux%u outside [1, %u]^2", width, height,
+                  FRM_MAX_DIMENSION);
+    return apply_panorama(ctx, width, height, ctx->panorama);
+  }
   // an adaptive frame's refined pixels are those of its full supersampled counterpart: the same bound
   const uint32_t factor = ctx->adaptive > 1u ? ctx->adaptive : ctx->supersample;
   const uint32_t limit = FRM_MAX_DIMENSION / factor;
@@ -331,6 +363,11 @@ int frm_set_supersampling(frm_ctx* ctx, uint32_t factor) {
   if (factor == 0 || factor > FRM_MAX_SUPERSAMPLE)
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "supersampling factor %u outside [1, %u]; factor not changed", factor,
                 FRM_MAX_SUPERSAMPLE);
+  if (factor > 1u && ctx->panorama)
+    return fail(ctx, FRM_ERR_UNSUPPORTED,
+                "supersampling factor %u on a panorama context (frm_set_panorama): switch that off first; "
+                "factor not changed",
+                factor);
   if (factor > 1u && ctx->adaptive > 1u)
     return fail(ctx, FRM_ERR_UNSUPPORTED,
                 "supersampling factor %u on an adaptive context (frm_set_adaptive): switch that off first; "
@@ -388,6 +425,11 @@ int frm_set_adaptive(frm_ctx* ctx, uint32_t factor, uint32_t threshold) {
                 "adaptive factor %u: the %ux%u frame's samples would lie on a frame above %u texels a side; values "
                 "not changed",
                 factor, ctx->out_width, ctx->out_height, FRM_MAX_DIMENSION);
+  if (factor > 1u && ctx->panorama)
+    return fail(ctx, FRM_ERR_UNSUPPORTED,
+                "adaptive factor %u on a panorama context (frm_set_panorama): switch that off first; values "
+                "not changed",
+                factor);
   if (factor > 1u && ctx->supersample > 1u)
     return fail(ctx, FRM_ERR_UNSUPPORTED,
                 "adaptive factor %u on a supersampled context (frm_set_supersampling): switch that off first; values "
@@ -527,10 +569,13 @@ int frm_set_parameters(frm_ctx* ctx, const frm_parameters* parameters) {
   return FRM_OK;
 }
 
+static int render_panorama(frm_ctx* ctx, frm_stats* stats);
+
 int frm_render(frm_ctx* ctx, frm_stats* stats) {
   int rc = ensure_ready(ctx);
   if (rc) return rc;
   if (ctx->group) return group_render(ctx, stats);
+  if (ctx->panorama) return render_panorama(ctx, stats);
   if (!stats && ring_eligible(ctx)) return ring_render(ctx);
   FRM_HIP(ctx, hipSetDevice(ctx->device));
   if ((rc = ring_quiesce(ctx))) return rc;  // a frame outside the ring: the ring's frames first
@@ -752,6 +797,7 @@ int frm_render_bands(frm_ctx* ctx, uint8_t* dev_dst, size_t dst_bytes, uint32_t 
   if (ctx->group) return not_on_group(ctx, "frm_render_bands");
   if (ctx->supersample > 1u) return not_supersampled(ctx, "frm_render_bands");
   if (ctx->adaptive > 1u) return not_adaptive(ctx, "frm_render_bands");
+  if (ctx->panorama) return not_panorama(ctx, "frm_render_bands");
   if (!dev_dst || band_rows == 0 || band_stride == 0)
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "invalid dst or band geometry");
   uint32_t rows = band_local_rows(ctx->height, band_rows, first_band, band_stride);
@@ -819,6 +865,7 @@ int frm_render_bands_batch(frm_ctx* ctx, uint32_t count, const frm_parameters* p
   if (ctx->group) return not_on_group(ctx, "frm_render_bands_batch");
   if (ctx->supersample > 1u) return not_supersampled(ctx, "frm_render_bands_batch");
   if (ctx->adaptive > 1u) return not_adaptive(ctx, "frm_render_bands_batch");
+  if (ctx->panorama) return not_panorama(ctx, "frm_render_bands_batch");
   if (!ctx->width) return fail(ctx, FRM_ERR_NOT_READY, "frm_resize has not been called");
   if (!params || !dev_dst || count == 0 || count > FRM_MAX_BATCH || band_rows == 0 || band_stride == 0)
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "invalid batch (count %u, at most %u) or band geometry", count,
@@ -895,6 +942,7 @@ int frm_render_shutter(frm_ctx* ctx, uint32_t count, const frm_parameters* param
   if (ctx->group) return not_on_group(ctx, "frm_render_shutter");
   if (ctx->adaptive > 1u)
     return fail(ctx, FRM_ERR_UNSUPPORTED, "frm_render_shutter: not available on an adaptive context (frm_set_adaptive)");
+  if (ctx->panorama) return not_panorama(ctx, "frm_render_shutter");
   if (!ctx->width) return fail(ctx, FRM_ERR_NOT_READY, "frm_resize has not been called");
   for (uint32_t k = 0; k < count; ++k) {
     SceneUniforms sk;
@@ -1009,12 +1057,169 @@ int frm_accumulate(frm_ctx* ctx, const uint8_t* dev_src, size_t src_bytes, size_
   return FRM_OK;
 }
 
+// frm_render of a panorama context: frm_render_shutter's steps with the six faces as the batch and
+// the projection in the place of the accumulation.
+static int render_panorama(frm_ctx* ctx, frm_stats* stats) {
+  FRM_HIP(ctx, hipSetDevice(ctx->device));
+  int rc = ring_quiesce(ctx);  // a frame outside the ring: the ring's frames first
+  if (rc) return rc;
+  ctx->last_is_ring = false;
+  if (stats && (rc = synchronize_all(ctx))) return rc;  // the counters must hold this frame alone
+  frm_parameters faces[6];
+  frm_panorama_parameters(&ctx->params, ctx->panorama, faces);
+  const uint32_t si = ctx->next_slot;
+  Slot* sl = nullptr;
+  hipStream_t s;
+  if ((rc = begin_frame(ctx, &sl, &s))) return rc;
+  const size_t face_bytes = (size_t)ctx->width * ctx->height * 4u;
+  // the frame shown() hands out is the panorama: the slot's framebuffer holds it, the faces are scratch
+  if ((rc = ensure_fb(ctx, *sl, (size_t)ctx->out_width * ctx->out_height * 4u)) ||
+      (rc = ensure_panorama(ctx, *sl, 6u * face_bytes, ctx->out_width, ctx->out_height)))
+    return rc;
+  sl->adaptive[sl->fb_idx] = false;
+  if (stats && (rc = stats_begin(ctx, s))) return rc;
+  // the faces differ in their cameras alone (frm_panorama_parameters)
+  SceneUniforms s0;
+  float powers[FRM_MAX_BATCH];
+  bool anim = false;
+  (void)batch_uniforms(ctx, 6, faces, &s0, powers, &anim);
+  KernelArgs a = make_args(ctx, faces[0], s0, sl->pano_src.p, ctx->counters, ctx->height, 0, 1, ctx->height);
+  // every launch of the frame runs on its slot (launch() takes the context's next one and moves on)
+  if (batch_shares_launch(ctx, a, 6, anim)) {
+    set_batch(ctx, a, 6, faces, powers, anim, face_bytes);
+    ctx->next_slot = si;
+    if ((rc = launch(ctx, a, s))) return rc;
+  } else {
+    for (uint32_t k = 0; k < 6u; ++k) {
+      a = make_args(ctx, faces[k], s0, sl->pano_src.p + k * face_bytes, ctx->counters, ctx->height, 0, 1, ctx->height);
+      ctx->next_slot = si;
+      if ((rc = launch(ctx, a, s))) return rc;
+    }
+  }
+  FRM_HIP(ctx, launch_project_equirect(sl->pano_src.p, face_bytes, ctx->panorama, (const float*)sl->pano_tables.p,
+                                       sl->fb(), ctx->out_width, ctx->out_height, s));
+  FRM_HIP(ctx, hipEventRecord(sl->done, s));  // covers the projection
+  show_slot(ctx, *sl);
+  ctx->panorama_seq = ctx->render_seq;
+  keep_render_params(ctx);
+  if (stats) {
+    uint64_t host[FRM_NUM_COUNTERS];
+    float ms = 0.0f;
+    if ((rc = stats_end(ctx, s, host, &ms)) || (rc = frm_stats_from_counters(ctx, host, stats))) return rc;
+    stats->kernel_ms = ms;
+  }
+  return FRM_OK;
+}
+
+int frm_set_panorama(frm_ctx* ctx, uint32_t face_size) {
+  if (!ctx) return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (face_size) {
+    if (ctx->group) return not_on_group(ctx, "frm_set_panorama");
+    if (ctx->supersample > 1u) return not_supersampled(ctx, "frm_set_panorama");
+    if (ctx->adaptive > 1u) return not_adaptive(ctx, "frm_set_panorama");
+    // the six faces are one batch in one scratch: 1 GiB of it at most, and a shared launch's u32
+    // fetch positions (frm_render_bands_batch)
+    const uint64_t m = (uint64_t)face_size + 2u, npix = 6u * m * m;
+    if (m > FRM_MAX_DIMENSION || npix * 4u > (1ull << 30) || npix >= 0xFFFFFFFFull - kQueueHeadroom)
+      return fail(ctx, FRM_ERR_INVALID_ARGUMENT,
+                  "panorama face size %u: six faces of %llu texels a side exceed %u a side or 1 GiB; face size not "
+                  "changed",
+                  face_size, (unsigned long long)m, FRM_MAX_DIMENSION);
+  }
+  if (face_size == ctx->panorama) return FRM_OK;
+  // No drain: frames in flight and their tickets keep their bytes; like a size change, there is no
+  // frame under the new setting for the async readbacks until the next frm_render.
+  if (!ctx->out_width) {
+    ctx->panorama = face_size;
+    return FRM_OK;
+  }
+  FRM_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = ring_leave(ctx)) return rc;
+  if (face_size) return apply_panorama(ctx, ctx->out_width, ctx->out_height, face_size);
+  if (int rc = apply_size(ctx, ctx->out_width, ctx->out_height, ctx->supersample)) return rc;
+  ctx->panorama = 0;
+  ctx->render_seq = 0;
+  return FRM_OK;
+}
+
+int frm_get_panorama(const frm_ctx* ctx, uint32_t* out_face_size) {
+  if (!ctx || !out_face_size) return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "ctx/out_face_size is NULL");
+  *out_face_size = ctx->panorama;
+  return FRM_OK;
+}
+
+int frm_panorama_face_size(uint32_t width, uint32_t* out_face_size) {
+  if (!out_face_size || width == 0 || width > FRM_MAX_DIMENSION)
+    return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "out_face_size is NULL or width %u outside [1, %u]", width,
+                FRM_MAX_DIMENSION);
+  *out_face_size = (width + 3u) / 4u;
+  return FRM_OK;
+}
+
+int frm_equirect_tables(uint32_t width, uint32_t height, float* sin_lon, float* cos_lon, float* sin_lat,
+                        float* cos_lat) {
+  if (!sin_lon || !cos_lon || !sin_lat || !cos_lat || width == 0 || height == 0 || width > FRM_MAX_DIMENSION ||
+      height > FRM_MAX_DIMENSION)
+    return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "a table is NULL or size %ux%u outside [1, %u]^2", width, height,
+                FRM_MAX_DIMENSION);
+  float* t = new (std::nothrow) float[2u * (size_t)width + 2u * (size_t)height];
+  if (!t) return fail(nullptr, FRM_ERR_OUT_OF_MEMORY, "host allocation failed");
+  equirect_tables(width, height, t);
+  memcpy(sin_lon, t, width * sizeof(float));
+  memcpy(cos_lon, t + width, width * sizeof(float));
+  memcpy(sin_lat, t + 2u * (size_t)width, height * sizeof(float));
+  memcpy(cos_lat, t + 2u * (size_t)width + height, height * sizeof(float));
+  delete[] t;
+  return FRM_OK;
+}
+
+int frm_project_equirect(frm_ctx* ctx, const uint8_t* dev_faces, size_t faces_bytes, size_t face_stride_bytes,
+                         uint32_t face_size, uint8_t* dev_dst, size_t dst_bytes, uint32_t out_width,
+                         uint32_t out_height, void* stream) {
+  if (!ctx || !dev_faces || !dev_dst) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "ctx/dev_faces/dev_dst is NULL");
+  if (face_size == 0 || face_size > FRM_MAX_DIMENSION - 2u)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "face size %u outside [1, %u]", face_size, FRM_MAX_DIMENSION - 2u);
+  if (out_width == 0 || out_height == 0 || out_width > FRM_MAX_DIMENSION || out_height > FRM_MAX_DIMENSION)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "output size %ux%u outside [1, %u]^2", out_width, out_height,
+                FRM_MAX_DIMENSION);
+  const size_t m = (size_t)face_size + 2u, face_need = m * m * 4u;
+  const uintptr_t fa = reinterpret_cast<uintptr_t>(dev_faces), da = reinterpret_cast<uintptr_t>(dev_dst);
+  if (fa % 4u || da % 4u) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "dev_faces / dev_dst not 4-byte aligned");
+  if (face_stride_bytes % 4u || face_stride_bytes < face_need)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "face stride %zu: below a face's %zu bytes or not a multiple of 4",
+                face_stride_bytes, face_need);
+  if (faces_bytes < face_need || (faces_bytes - face_need) / face_stride_bytes < 5u)
+    return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "faces hold %zu bytes, six faces %zu bytes apart need %zu", faces_bytes,
+                face_stride_bytes, 5u * face_stride_bytes + face_need);
+  const size_t src_need = 5u * face_stride_bytes + face_need, dst_need = (size_t)out_width * out_height * 4u;
+  if (dst_bytes < dst_need)
+    return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "dst holds %zu bytes, the panorama needs %zu", dst_bytes, dst_need);
+  if (fa < da + dst_need && da < fa + src_need)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "dev_faces and dev_dst overlap");
+  FRM_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = ring_leave(ctx)) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  // the tables are scratch per call, allocated and released in the order of the call's stream: calls
+  // in flight on different streams never share them
+  float* tables = nullptr;
+  int rc = dev_alloc(ctx, (void**)&tables, (2u * (size_t)out_width + 2u * (size_t)out_height) * sizeof(float), s);
+  if (rc) return rc;
+  hipError_t e = hipSuccess;
+  if (!(rc = upload_tables(ctx, tables, out_width, out_height, s)))
+    e = launch_project_equirect(dev_faces, face_stride_bytes, face_size, tables, dev_dst, out_width, out_height, s);
+  const int r1 = dev_release(ctx, tables, s);
+  if (rc) return rc;
+  if (e != hipSuccess) return hip_fail(ctx, e, "launch_project_equirect");
+  return r1;
+}
+
 int frm_unshuffle_bands(frm_ctx* ctx, const uint8_t* dev_src, size_t rank_stride_bytes, uint8_t* dev_dst,
                         size_t dst_bytes, uint32_t band_rows, uint32_t ranks, void* stream) {
   if (!ctx || !dev_src || !dev_dst || band_rows == 0 || ranks == 0)
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "invalid unshuffle arguments");
   if (ctx->supersample > 1u) return not_supersampled(ctx, "frm_unshuffle_bands");
   if (ctx->adaptive > 1u) return not_adaptive(ctx, "frm_unshuffle_bands");
+  if (ctx->panorama) return not_panorama(ctx, "frm_unshuffle_bands");
   if (!ctx->width) return fail(ctx, FRM_ERR_NOT_READY, "frm_resize has not been called");
   size_t need = (size_t)ctx->width * ctx->height * 4u;
   if (dst_bytes < need)
@@ -1109,6 +1314,8 @@ int frm_debug_trace(frm_ctx* ctx, float* out, size_t n_floats) {
   const Slot& sl = ctx->slots[ctx->last_slot];
   if (ctx->render_seq && ctx->shutter_seq == ctx->render_seq && !ctx->last_is_ring)
     return fail(ctx, FRM_ERR_NOT_READY, "the last frame was a frm_render_shutter frame: no single frame to trace");
+  if (ctx->render_seq && ctx->panorama_seq == ctx->render_seq && !ctx->last_is_ring)
+    return fail(ctx, FRM_ERR_NOT_READY, "the last frame was a panorama (frm_set_panorama): no single frame to trace");
   if (!ctx->render_seq || sl.seq != ctx->render_seq)
     return fail(ctx, FRM_ERR_NOT_READY, "no frm_render, or a later launch reused its slot's records");
   if (!sl.records.p || sl.records.cap < npix * kRecordBytes || !sl.sched_whole || sl.sched_w != ctx->width || sl.sched_h != ctx->height)

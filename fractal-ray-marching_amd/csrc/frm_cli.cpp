@@ -10,6 +10,12 @@
 //              [--frames F] [--dt S] [--keys BITS] [--orbit RAD_PER_S]
 //              [--lock-yaw 0..4] [--lock-pitch] [--time-factor X] [--gpus N] [--batch B]
 //              [--ssaa K] [--adaptive S] [--edge-threshold T] [--shutter-samples T] [--shutter F]
+//              [--panorama] [--face-size N]
+// With --panorama every frame is a 360-degree equirectangular one around the camera
+// (frm_set_panorama): --width / --height are the panorama's size, the six cube faces have N texels
+// a side (--face-size, default frm_panorama_face_size(W) = ceil(W / 4)) and the JSON lines count all
+// six. Works with --frames / --orbit / --out pattern; not with --ssaa, --adaptive,
+// --shutter-samples, --batch or --gpus.
 // With --shutter-samples T (1..32, default 1) every frame is motion-blurred: the mean, in linear
 // light, of T sub-frames that step the frame's own state (time, camera) through the fraction F
 // (--shutter, 0 < F <= 1, default 0.5) of --dt (frm_shutter_parameters, frm_render_shutter). The main
@@ -130,7 +136,7 @@ static int render_batched(frm_ctx* ctx, frm_parameters p, frm_camera cam, frm_ti
              "\"pos\": [%.5f, %.5f, %.5f], \"yaw\": %.5f, \"pitch\": %.5f, \"kernel_ms\": %.3f, "
              "\"batch\": %u, \"launch_march_steps\": %llu, \"launch_hit_pixels\": %llu, \"gsteps_per_s\": %.3f, "
              "\"ssaa\": %u, \"adaptive\": %u, \"edge_threshold\": %u, \"refined_pixels\": %llu, "
-             "\"shutter_samples\": 1, \"shutter\": %.6f}\n",
+             "\"shutter_samples\": 1, \"shutter\": %.6f, \"panorama\": 0, \"face_size\": 0}\n",
              fr, name, width, height, ps[fr].time, cams[fr].position[0], cams[fr].position[1], cams[fr].position[2],
              cams[fr].yaw, cams[fr].pitch, ms / n, n, (unsigned long long)(c[2] + c[3]), (unsigned long long)c[1],
              (double)(c[2] + c[3]) / (ms * 1e-3) / 1e9, ssaa, adaptive, edge_threshold,
@@ -160,6 +166,8 @@ int main(int argc, char** argv) {
   bool ssaa_given = false, adaptive_given = false;
   uint32_t shutter_samples = 1;  // sub-frames per frame
   float shutter = 0.5f;          // the fraction of dt they span
+  bool panorama = false;
+  uint32_t face_size = 0;  // 0: frm_panorama_face_size(width)
   for (int i = 1; i < argc; ++i) {
     const char* a = argv[i];
     auto next = [&](void) -> const char* {
@@ -231,7 +239,32 @@ int main(int argc, char** argv) {
         return 2;
       }
     }
+    else if (!strcmp(a, "--panorama")) panorama = true;
+    else if (!strcmp(a, "--face-size")) {
+      const char* v = next();
+      char* end = nullptr;
+      const long k = strtol(v, &end, 10);
+      if (end == v || *end || k < 1 || k > (long)FRM_MAX_DIMENSION - 2) {
+        fprintf(stderr, "frm_render: --face-size %s outside [1, %u]\n", v, FRM_MAX_DIMENSION - 2u);
+        return 2;
+      }
+      face_size = (uint32_t)k;
+    }
     else { fprintf(stderr, "unknown argument %s\n", a); return 2; }
+  }
+  if (face_size && !panorama) {
+    fprintf(stderr, "frm_render: --face-size needs --panorama\n");
+    return 2;
+  }
+  if (panorama && (ssaa_given || adaptive_given || shutter_samples > 1 || batch > 1 || gpus > 0)) {
+    fprintf(stderr, "frm_render: --panorama excludes --ssaa, --adaptive, --shutter-samples, --batch and --gpus (for an "
+                    "anti-aliased panorama project the faces to a larger frame with frm_project_equirect and "
+                    "frm_resolve it)\n");
+    return 2;
+  }
+  if (panorama && !face_size && frm_panorama_face_size(width, &face_size) != FRM_OK) {
+    fprintf(stderr, "frm_render: --panorama: %s\n", frm_last_error(nullptr));
+    return 2;
   }
   if (ssaa_given && adaptive_given) {
     fprintf(stderr, "frm_render: --adaptive / --edge-threshold and --ssaa exclude each other\n");
@@ -280,6 +313,7 @@ int main(int argc, char** argv) {
     check(frm_set_supersampling(ctx, ssaa), ctx, "frm_set_supersampling");
     check(frm_resize(ctx, width, height), ctx, "frm_resize");
     check(frm_set_adaptive(ctx, adaptive, edge_threshold), ctx, "frm_set_adaptive");
+    if (panorama) check(frm_set_panorama(ctx, face_size), ctx, "frm_set_panorama");
   }
   std::vector<uint8_t> rgba((size_t)width * height * 4);
   if (batch < 1 || batch > FRM_MAX_BATCH) {
@@ -321,12 +355,12 @@ int main(int argc, char** argv) {
            "\"pos\": [%.5f, %.5f, %.5f], \"yaw\": %.5f, \"pitch\": %.5f, \"kernel_ms\": %.3f, "
            "\"march_steps\": %llu, \"hit_pixels\": %llu, \"gsteps_per_s\": %.3f, \"ssaa\": %u, "
            "\"adaptive\": %u, \"edge_threshold\": %u, \"refined_pixels\": %llu, \"shutter_samples\": %u, "
-           "\"shutter\": %.6f}\n",
+           "\"shutter\": %.6f, \"panorama\": %u, \"face_size\": %u}\n",
            fr, name, width, height, p.time, cam.position[0], cam.position[1], cam.position[2], cam.yaw,
            cam.pitch, st.kernel_ms, (unsigned long long)st.march_steps, (unsigned long long)st.hit_pixels,
            st.march_steps / (st.kernel_ms * 1e-3) / 1e9, ssaa, adaptive, edge_threshold,
            (unsigned long long)(adaptive > 1 ? (st.pixels - (uint64_t)width * height) / (adaptive * adaptive) : 0),
-           shutter_samples, shutter);
+           shutter_samples, shutter, panorama ? 1u : 0u, face_size);
   }
   frm_destroy(ctx);
   return 0;

@@ -89,6 +89,10 @@ struct Slot {
   // motion blur (frm_render_shutter): the sub-frames of one chunk, back to back, and the f32 sums a
   // frame of several chunks carries between them (a float4 per output pixel)
   PoolBuf shutter_src, shutter_acc;
+  // panoramas (frm_set_panorama): the six faces of a frame, back to back, and the direction tables
+  // (equirect_tables) of a pano_w x pano_h output, uploaded when the output size changes
+  PoolBuf pano_src, pano_tables;
+  uint32_t pano_w = 0, pano_h = 0;
   unsigned int* queue = nullptr;
   PoolBuf records;  // persistent kernel scratch (ShadeGeom[n] then ShadeTail[n], record_tails), grown on demand
   // pixel scheduling state (frm_sched.hip), sched_cap entries each: 0..cap-1, the fetch
@@ -244,6 +248,15 @@ struct frm_ctx {
   SceneUniforms scene{};
   uint32_t shutter_chunk = FRM_MAX_SHUTTER_SAMPLES;  // frm_render_shutter: sub-frames per chunk at most (FRM_SHUTTER_CHUNK)
   uint64_t shutter_seq = 0;  // render_seq of the last frm_render_shutter (0: none)
+  uint32_t panorama = 0;      // frm_set_panorama: the face size N (0: off); the render size is (N + 2)^2
+  uint64_t panorama_seq = 0;  // render_seq of the last panorama frm_render (0: none)
+  // host copies of direction tables whose upload may still be running: each is released once the
+  // event recorded after its copy has completed (upload_tables), the rest by frm_destroy
+  struct HostBlock {
+    float* p;
+    hipEvent_t copied;
+  };
+  std::vector<HostBlock> host_blocks;
   Ring ring;
   bool ring_enabled = false;  // FRM_RING=1: the resident frame ring (opt-in: slower)
   bool last_is_ring = false; // the last frm_render posted a ring frame (ring.last_seq)
@@ -282,6 +295,9 @@ int select_fb(frm_ctx* ctx, Slot& sl, uint32_t i);
 int ensure_res(frm_ctx* ctx, Slot& sl, size_t bytes);
 int resolve_frame(frm_ctx* ctx, Slot& sl);
 int ensure_shutter(frm_ctx* ctx, Slot& sl, size_t src_bytes, size_t acc_bytes);
+int upload_tables(frm_ctx* ctx, float* dev, uint32_t w, uint32_t h, hipStream_t s);
+void release_host_blocks(frm_ctx* ctx, bool wait);
+int ensure_panorama(frm_ctx* ctx, Slot& sl, size_t src_bytes, uint32_t w, uint32_t h);
 const uint8_t* shown(const frm_ctx* ctx, const Slot& sl);
 uint32_t band_local_rows(uint32_t height, uint32_t band_rows, uint32_t first, uint32_t stride);
 uint32_t group_band_rows(uint32_t height, uint32_t n);

@@ -374,3 +374,46 @@ extern "C" void frm_shutter_parameters(const frm_parameters* p, const frm_camera
     out[s] = p2;
   }
 }
+
+// ---- panoramas (frm.h "panorama") ------------------------------------------------------------
+namespace {
+// The face bases in the camera's own basis (x right, y up, z forward): r, u, w of face f. Every
+// vector is +- a unit vector: kFaceAxis the component that is not zero, kFaceSign its sign.
+constexpr int kFaceAxis[6][3] = {{0, 1, 2}, {0, 1, 2}, {2, 1, 0}, {2, 1, 0}, {0, 2, 1}, {0, 2, 1}};
+constexpr int kFaceSign[6][3] = {{1, 1, 1}, {-1, 1, -1}, {-1, 1, 1}, {1, 1, -1}, {1, -1, 1}, {1, 1, -1}};
+}  // namespace
+
+extern "C" void frm_panorama_parameters(const frm_parameters* p, uint32_t face_size, frm_parameters out[6]) {
+  if (!p || !out || face_size == 0) return;
+  const float q = (float)(face_size + 2u) / (float)face_size;
+  const float a = frm::kCameraDirectionZ * q;
+  for (int f = 0; f < 6; ++f) {
+    frm_parameters pf = *p;
+    pf.aspect_scale[0] = pf.aspect_scale[1] = a;
+    for (int j = 0; j < 4; ++j)  // C_f = C * [r u w]: a signed permutation of C's first three columns
+      for (int i = 0; i < 3; ++i) {
+        const float c = p->camera_matrix[4 * j + kFaceAxis[f][i]];
+        pf.camera_matrix[4 * j + i] = kFaceSign[f][i] > 0 ? c : -c;
+      }
+    out[f] = pf;
+  }
+}
+
+namespace frm {
+// sin_lon[w], cos_lon[w], sin_lat[h], cos_lat[h] back to back: each computed in double precision and
+// rounded once to f32 (frm.h frm_equirect_tables).
+void equirect_tables(uint32_t w, uint32_t h, float* out) {
+  const double pi = 3.14159265358979323846;
+  for (uint32_t x = 0; x < w; ++x) {
+    const double lon = ((double)(2u * x + 1u) / (double)w - 1.0) * pi;
+    out[x] = (float)sin(lon);
+    out[w + x] = (float)cos(lon);
+  }
+  float* lat_t = out + 2u * (size_t)w;
+  for (uint32_t y = 0; y < h; ++y) {
+    const double lat = (1.0 - (double)(2u * y + 1u) / (double)h) * (pi / 2.0);
+    lat_t[y] = (float)sin(lat);
+    lat_t[h + y] = (float)cos(lat);
+  }
+}
+}  // namespace frm

@@ -256,6 +256,12 @@ hipError_t launch_resolve(const uint8_t* src, uint8_t* dst, uint32_t dw, uint32_
 // is stored back to; dst: nullptr, or dh rows of dw texels that receive encode(sum / divisor).
 hipError_t launch_shutter(const uint8_t* src, size_t frame_stride_bytes, uint32_t count, float* acc, uint8_t* dst,
                           uint32_t dw, uint32_t dh, uint32_t factor, uint32_t divisor, hipStream_t stream);
+// Panorama (frm_set_panorama, frm_project_equirect; frm_panorama_kernels.h): six cube faces
+// face_stride_bytes (a multiple of 4) apart in faces, each (n + 2)^2 RGBA8 sRGB texels, 4-byte
+// aligned, projected to dh rows of dw texels in dst. tables: equirect_tables' 2*dw + 2*dh floats
+// in device memory.
+hipError_t launch_project_equirect(const uint8_t* faces, size_t face_stride_bytes, uint32_t n, const float* tables,
+                                   uint8_t* dst, uint32_t dw, uint32_t dh, hipStream_t stream);
 // Adaptive supersampling (frm_set_adaptive, frm_refine; frm_refine_kernels.h): dst = src with alpha
 // 255 (height rows of width RGBA8 sRGB texels, both 4-byte aligned, not overlapping), except the
 // pixels whose 3 x 3 neighbourhood in src has a contrast >= threshold: those are the box resolve

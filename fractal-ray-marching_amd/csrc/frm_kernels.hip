@@ -12,6 +12,7 @@
 #include "frm_render_kernels.h"
 #include "frm_refine_kernels.h"
 #include "frm_shutter_kernels.h"
+#include "frm_panorama_kernels.h"
 
 namespace frm {
 

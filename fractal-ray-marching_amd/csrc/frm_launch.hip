@@ -64,6 +64,55 @@ int ensure_shutter(frm_ctx* ctx, Slot& sl, size_t src_bytes, size_t acc_bytes) {
   if (int rc = pool_grow(ctx, sl.shutter_src, src_bytes, sl.stream)) return rc;
   return pool_grow(ctx, sl.shutter_acc, acc_bytes, sl.stream);
 }
+// Releases the host copies of uploaded tables whose copy has completed (wait: all of them, each
+// waited for: frm_destroy).
+void release_host_blocks(frm_ctx* ctx, bool wait) {
+  size_t kept = 0;
+  for (frm_ctx::HostBlock& b : ctx->host_blocks) {
+    if (wait) (void)hipEventSynchronize(b.copied);
+    if (wait || hipEventQuery(b.copied) == hipSuccess) {
+      (void)hipEventDestroy(b.copied);
+      free(b.p);
+    } else {
+      ctx->host_blocks[kept++] = b;
+    }
+  }
+  ctx->host_blocks.resize(kept);
+}
+// The direction tables of a w x h panorama (equirect_tables: 2*w + 2*h floats) copied to dev in
+// the order of stream s. The host copy lives until an event recorded after the transfer has
+// completed, whether or not the runtime stages the transfer before it returns.
+int upload_tables(frm_ctx* ctx, float* dev, uint32_t w, uint32_t h, hipStream_t s) {
+  release_host_blocks(ctx, false);
+  const size_t bytes = (2u * (size_t)w + 2u * (size_t)h) * sizeof(float);
+  frm_ctx::HostBlock b{(float*)malloc(bytes), nullptr};
+  if (!b.p) return fail(ctx, FRM_ERR_OUT_OF_MEMORY, "host allocation failed");
+  equirect_tables(w, h, b.p);
+  hipError_t e = hipEventCreateWithFlags(&b.copied, hipEventDisableTiming);
+  if (e != hipSuccess) {
+    free(b.p);
+    return hip_fail(ctx, e, "hipEventCreateWithFlags");
+  }
+  ctx->host_blocks.push_back(b);  // released only after the event, also when a call below fails
+  e = hipMemcpyAsync(dev, b.p, bytes, hipMemcpyHostToDevice, s);
+  const hipError_t e2 = hipEventRecord(b.copied, s);
+  if (e != hipSuccess) return hip_fail(ctx, e, "hipMemcpyAsync");
+  if (e2 != hipSuccess) return hip_fail(ctx, e2, "hipEventRecord");
+  return FRM_OK;
+}
+// The slot's panorama scratch for six faces of src_bytes in all and the tables of a w x h output,
+// grown (and the tables uploaded, when the output size is new to the slot) on the slot stream: the
+// slot's last panorama ran there.
+int ensure_panorama(frm_ctx* ctx, Slot& sl, size_t src_bytes, uint32_t w, uint32_t h) {
+  if (int rc = pool_grow(ctx, sl.pano_src, src_bytes, sl.stream)) return rc;
+  if (sl.pano_w == w && sl.pano_h == h) return FRM_OK;
+  sl.pano_w = sl.pano_h = 0;
+  if (int rc = pool_grow(ctx, sl.pano_tables, (2u * (size_t)w + 2u * (size_t)h) * sizeof(float), sl.stream)) return rc;
+  if (int rc = upload_tables(ctx, (float*)sl.pano_tables.p, w, h, sl.stream)) return rc;
+  sl.pano_w = w;
+  sl.pano_h = h;
+  return FRM_OK;
+}
 // The second image of the slot's current framebuffer, on the slot stream, after the frame is
 // complete there: the box resolve of a supersampled context, or the adaptive frame of an adaptive
 // one (the edge pass over the frame, then the samples of its refined pixels; their work is added

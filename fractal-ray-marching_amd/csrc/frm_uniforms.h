@@ -24,5 +24,6 @@ void compute_scene_uniforms(const frm_parameters& p, uint32_t flags, SceneUnifor
 void compute_frame_uniforms(const frm_parameters& p, uint32_t width, uint32_t height,
                             uint32_t max_steps, FrameUniforms* f);
 uint64_t wom_ops(const SceneUniforms& u, const uint64_t* counters);
+void equirect_tables(uint32_t w, uint32_t h, float* out);  // 2*w + 2*h floats
 
 }  // namespace frm

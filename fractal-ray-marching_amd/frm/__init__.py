@@ -9,7 +9,8 @@ from ._lib import (FRM_DEFAULT_MAX_STEPS, FRM_FLAG_PERSISTENT_KERNEL, FRM_FLAG_S
                    FRM_ADAPTIVE_DEFAULT_THRESHOLD, FRM_MAX_SHUTTER_SAMPLES,
                    FrmError, LIB_PATH,
                    load)
-from .parameters import Camera, HeldKeys, Parameters, Timing, shutter_parameters
+from .parameters import (Camera, HeldKeys, Parameters, Timing, equirect_tables, panorama_face_size,
+                         panorama_parameters, shutter_parameters)
 from .renderer import Renderer, device_count
 from .workloads import FRAME_SECONDS, POSES, POWER8_TIME, WORKLOADS, Workload, frame_sequence, make_parameters
 
@@ -17,6 +18,7 @@ __all__ = [
     "Camera", "HeldKeys", "Parameters", "Renderer", "Timing", "FrmError", "device_count", "load", "LIB_PATH",
     "FRAME_SECONDS", "POSES", "POWER8_TIME", "WORKLOADS", "Workload", "frame_sequence", "make_parameters",
     "shutter_parameters", "FRM_MAX_SHUTTER_SAMPLES",
+    "panorama_parameters", "panorama_face_size", "equirect_tables",
     "FRM_DEFAULT_MAX_STEPS", "FRM_FLAG_PERSISTENT_KERNEL", "FRM_FLAG_SCENE_SPHERE", "FRM_FLAG_SIMPLE_KERNEL",
     "FRM_FLAG_UNBOUNDED_ITERATIONS", "FRM_FLAG_HW_MATH",
     "FRM_MAX_BATCH", "FRM_MAX_FRAMES_IN_FLIGHT", "FRM_MAX_NUM_ITERATIONS", "FRM_MAX_SUPERSAMPLE", "FRM_NUM_COUNTERS",

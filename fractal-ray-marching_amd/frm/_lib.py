@@ -193,6 +193,15 @@ SIGNATURES = [
     ("frm_shutter_parameters", None,
      [_P(FrmParameters), _P(FrmCamera), _P(FrmTiming), ctypes.c_uint32, ctypes.c_float, ctypes.c_uint32,
       ctypes.c_float, ctypes.c_void_p]),
+    ("frm_panorama_parameters", None, [_P(FrmParameters), ctypes.c_uint32, ctypes.c_void_p]),
+    ("frm_panorama_face_size", ctypes.c_int, [ctypes.c_uint32, _P(ctypes.c_uint32)]),
+    ("frm_equirect_tables", ctypes.c_int,
+     [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("frm_project_equirect", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p,
+      ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]),
+    ("frm_set_panorama", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
+    ("frm_get_panorama", ctypes.c_int, [ctypes.c_void_p, _P(ctypes.c_uint32)]),
 ]
 
 _lib = None

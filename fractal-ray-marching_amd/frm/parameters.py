@@ -222,3 +222,31 @@ def shutter_parameters(parameters, camera, timing, held_keys, dt, samples, shutt
                                        ctypes.byref(timing.raw), int(held_keys), float(dt), samples, float(shutter),
                                        ctypes.addressof(out))
     return [Parameters.from_bytes(ctypes.string_at(ctypes.addressof(out[k]), 96)) for k in range(samples)]
+
+
+def panorama_parameters(parameters, face_size):
+    """frm_panorama_parameters: the six cube-face Parameters (+z, -z, +x, -x, +y, -y) of a panorama
+    around `parameters`' camera, each an (face_size + 2)^2 frame with a one-texel guard band."""
+    face_size = int(face_size)
+    if face_size < 1:
+        raise ValueError("face_size must be at least 1")
+    out = (_lib.FrmParameters * 6)()
+    _lib.load().frm_panorama_parameters(ctypes.byref(parameters.raw), face_size, ctypes.addressof(out))
+    return [Parameters.from_bytes(ctypes.string_at(ctypes.addressof(out[k]), 96)) for k in range(6)]
+
+
+def panorama_face_size(width):
+    """frm_panorama_face_size: the default face size ceil(width / 4) of a panorama `width` pixels wide."""
+    n = ctypes.c_uint32()
+    _lib.check(_lib.load().frm_panorama_face_size(int(width), ctypes.byref(n)))
+    return n.value
+
+
+def equirect_tables(width, height):
+    """frm_equirect_tables: (sin_lon[width], cos_lon[width], sin_lat[height], cos_lat[height]) float32
+    arrays: the directions of a width x height equirectangular frame's columns and rows."""
+    import numpy as np
+
+    t = [np.empty(int(n), np.float32) for n in (width, width, height, height)]
+    _lib.check(_lib.load().frm_equirect_tables(int(width), int(height), *[a.ctypes.data for a in t]))
+    return tuple(t)

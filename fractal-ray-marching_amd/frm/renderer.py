@@ -12,9 +12,10 @@ from . import _lib
 
 class Renderer:
     def __init__(self, device=0, max_steps=0, flags=0, frames_in_flight=1, devices=None, supersampling=1,
-                 adaptive=None):
+                 adaptive=None, panorama=0):
         """supersampling: samples per pixel and axis (frm_set_supersampling; 1 = off).
         adaptive: (S, threshold) or S: S x S samples for the pixels on an edge only (frm_set_adaptive).
+        panorama: cube face size N; every frame is a 360-degree equirectangular one (frm_set_panorama; 0 = off).
         devices: a list of HIP device ordinals for a GROUP context (frm_config.device_count):
         every frame is row-tiled over them and gathered on devices[0] (RCCL, or device copies
         when a device repeats); the rest of the API is the same."""
@@ -37,11 +38,14 @@ class Renderer:
         self.width = self.height = 0
         self.supersampling = 1
         self._adaptive = (1, _lib.FRM_ADAPTIVE_DEFAULT_THRESHOLD)
+        self.panorama = 0
         try:
             if supersampling != 1:
                 self.set_supersampling(supersampling)
             if adaptive is not None:
                 self.set_adaptive(*(adaptive if isinstance(adaptive, (tuple, list)) else (adaptive,)))
+            if panorama:
+                self.set_panorama(panorama)
         except Exception:
             self.close()
             raise
@@ -80,11 +84,26 @@ class Renderer:
     # the internal render size: what trace(), pixel_keys() and set_pixel_keys() work on
     @property
     def render_width(self):
-        return self.width * self.supersampling
+        return self.panorama + 2 if self.panorama else self.width * self.supersampling
 
     @property
     def render_height(self):
-        return self.height * self.supersampling
+        return self.panorama + 2 if self.panorama else self.height * self.supersampling
+
+    def set_panorama(self, face_size):
+        """frm_set_panorama: from the next render on, every frame is the equirectangular projection, at
+        the resize() size, of six cube faces of (face_size + 2)^2 texels rendered around the camera;
+        0 switches it off."""
+        self._check(self._lib.frm_set_panorama(self.ctx, face_size))
+        self.panorama = int(face_size)
+
+    def project_equirect(self, faces_ptr, faces_bytes, face_stride, face_size, dst_ptr, dst_bytes, out_w, out_h,
+                         stream=0):
+        """frm_project_equirect: projects the six (face_size + 2)^2 RGBA8 sRGB cube faces face_stride
+        bytes apart at device pointer faces_ptr into the out_h x out_w equirectangular frame at dst_ptr,
+        asynchronously on `stream` (0: the context's)."""
+        self._check(self._lib.frm_project_equirect(self.ctx, faces_ptr, faces_bytes, face_stride, face_size, dst_ptr,
+                                                   dst_bytes, out_w, out_h, stream or None))
 
     def resolve(self, src_ptr, src_bytes, out_w, out_h, factor, dst_ptr, dst_bytes, stream=0):
         """frm_resolve: box-resolve (factor*out_h) x (factor*out_w) RGBA8 sRGB texels at device pointer

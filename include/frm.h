@@ -428,6 +428,83 @@ int frm_accumulate(frm_ctx* ctx, const uint8_t* dev_src, size_t src_bytes, size_
                    uint32_t count, uint32_t out_width, uint32_t out_height, uint32_t factor,
                    float* dev_acc, size_t acc_bytes, uint32_t divisor,
                    uint8_t* dev_dst, size_t dst_bytes, void* stream);
+/* ---- panorama: a 360-degree equirectangular frame of W x H pixels, projected from the six faces
+ *      of a cube map around the camera (no reference counterpart: the reference has one pinhole
+ *      camera). N is the face size, M = N + 2 (one guard texel all round), q = (float)M / (float)N
+ *      and a = kCameraDirectionZ * q (one f32 multiply; kCameraDirectionZ = f32(1/atan(pi/2)), the
+ *      z of every camera ray).
+ *      Face frames. Face f of a parameter set p is the M x M frame frm_render renders for p_f: p with
+ *      aspect_scale = (a, a) (the caller's aspect is ignored) and the camera C_f = C * [r_f u_f w_f],
+ *      C the 4x4 camera matrix of p and the face vectors in the camera's own basis (x right, y up,
+ *      z forward); column 3 is unchanged:
+ *          f  face       r (right)   u (up)      w (forward)
+ *          0  +z front   ( 1,0, 0)   (0,1, 0)    ( 0, 0, 1)
+ *          1  -z back    (-1,0, 0)   (0,1, 0)    ( 0, 0,-1)
+ *          2  +x right   ( 0,0,-1)   (0,1, 0)    ( 1, 0, 0)
+ *          3  -x left    ( 0,0, 1)   (0,1, 0)    (-1, 0, 0)
+ *          4  +y up      ( 1,0, 0)   (0,0,-1)    ( 0, 1, 0)
+ *          5  -y down    ( 1,0, 0)   (0,0, 1)    ( 0,-1, 0)
+ *      r x u = w for every face. C_f is a signed permutation of C's first three columns, exact in
+ *      f32: camera_matrix[4j+i] of p_f is + or - camera_matrix[4j+k] of p, for all four j. The inner
+ *      N x N texels cover tan in [-1, 1]; their centres sit where those of an N x N 90-degree face
+ *      would.
+ *      Direction tables. Output pixel (X, Y) has longitude lon = ((2X+1)/W - 1) * pi and latitude
+ *      lat = (1 - (2Y+1)/H) * pi/2: the image centre looks along the camera's forward axis, lon grows
+ *      to the right, row 0 is the zenith side. sin_lon[X], cos_lon[X], sin_lat[Y], cos_lat[Y] are
+ *      computed on the host in double precision and rounded once to f32.
+ *      Per pixel, all f32, no contraction, IEEE divisions:
+ *          dx = cos_lat*sin_lon;  dy = sin_lat;  dz = cos_lat*cos_lon
+ *          face: |dz| >= |dx| && |dz| >= |dy| ? (dz > 0 ? 0 : 1)
+ *              : |dx| >= |dy|                 ? (dx > 0 ? 2 : 3)
+ *              :                                (dy > 0 ? 4 : 5)
+ *          A = d.r_f;  B = d.u_f;  m = d.w_f        (each a signed component of d: no arithmetic)
+ *          u = A / m;  v = B / m
+ *          fx = u*(0.5f*N) + (0.5f*M - 0.5f);   fy = (0.5f*M - 0.5f) - v*(0.5f*N)
+ *          x0 = floor(fx); tx = fx - x0;  y0 = floor(fy); ty = fy - y0
+ *          x0, x0+1, y0, y0+1 clamped to [0, M-1]
+ *      then the blit's linear filter over the four texels t00 (x0, y0), t10 (x0+1, y0), t01, t11 of
+ *      face f: per channel top = mix(D[t00], D[t10], tx), bot = mix(D[t01], D[t11], tx),
+ *      c = mix(top, bot, ty) with mix(a, b, t) = a*(1.0f - t) + b*t and D the blit's sRGB decode
+ *      table; stored as the sRGB store does, alpha 255 (the source alpha is ignored). The filter
+ *      is 2 x 2 everywhere: near the cube's corners, where face texels are denser than panorama
+ *      pixels, it does not filter the minification.
+ * frm_panorama_parameters: out[f] = p_f for f = 0..5 (host only; nothing for NULL or face_size 0).
+ * frm_panorama_face_size: the product default N = ceil(width / 4) for a panorama `width` pixels
+ *      wide: the customary cube size for an equirectangular width (the equator then has about one
+ *      face texel per pixel), not a measured optimum. width in [1, FRM_MAX_DIMENSION].
+ * frm_equirect_tables: the four tables above (width, width, height, height floats; host only).
+ * frm_project_equirect: the projection alone, on any context, asynchronous on `stream` (NULL: the
+ *      context's). dev_faces holds faces 0..5 face_stride_bytes apart (a multiple of 4, at least
+ *      4*M*M), each M rows of M RGBA8 sRGB texels; dev_dst receives out_height rows of out_width
+ *      texels. Both device memory of the context's GPU, 4-byte aligned, not overlapping; face_size
+ *      in [1, FRM_MAX_DIMENSION - 2], the output sizes in [1, FRM_MAX_DIMENSION]
+ *      (FRM_ERR_INVALID_ARGUMENT otherwise; FRM_ERR_BUFFER_TOO_SMALL when faces_bytes or dst_bytes
+ *      is short). The tables are scratch of the call, allocated and released in its stream's order.
+ * frm_set_panorama: face size N; 0 (the default) is off, allocates nothing and changes no path.
+ *      With N >= 1 frm_resize keeps taking the output size W x H (any, up to FRM_MAX_DIMENSION)
+ *      while the context renders M x M frames: every frm_render renders the six faces of the
+ *      context's parameters into a scratch of its slot (one shared persistent launch where
+ *      frm_render_bands_batch's rules allow it, else six launches, with the same bytes) and projects
+ *      them into the frame that frm_read_frame, frm_present, their async forms and frm_frame_pixels
+ *      see. It takes one render slot as frm_render does; a change acts as frm_resize does: no drain,
+ *      frames in flight and their tickets keep their bytes, async readbacks give FRM_ERR_NOT_READY
+ *      until the next frm_render. frm_stats is the sum over the faces (pixels = 6*M*M); kernel_ms
+ *      includes the projection. frm_debug_trace after a panorama gives FRM_ERR_NOT_READY (no single
+ *      frame to trace); panoramas never go through the resident ring. FRM_ERR_UNSUPPORTED, with
+ *      nothing changed: N >= 1 on a group, supersampled or adaptive context; and on a panorama
+ *      context frm_set_supersampling(k > 1), frm_set_adaptive(k > 1), frm_render_shutter,
+ *      frm_render_bands, frm_render_bands_batch and frm_unshuffle_bands. FRM_ERR_INVALID_ARGUMENT
+ *      (N unchanged) when M exceeds FRM_MAX_DIMENSION or the six faces 1 GiB.
+ *      Additive: FRM_ABI_VERSION stays 5. */
+void frm_panorama_parameters(const frm_parameters* p, uint32_t face_size, frm_parameters out[6]);
+int frm_panorama_face_size(uint32_t width, uint32_t* out_face_size);
+int frm_equirect_tables(uint32_t width, uint32_t height, float* sin_lon, float* cos_lon, float* sin_lat,
+                        float* cos_lat);
+int frm_project_equirect(frm_ctx* ctx, const uint8_t* dev_faces, size_t faces_bytes, size_t face_stride_bytes,
+                         uint32_t face_size, uint8_t* dev_dst, size_t dst_bytes, uint32_t out_width,
+                         uint32_t out_height, void* stream);
+int frm_set_panorama(frm_ctx* ctx, uint32_t face_size);
+int frm_get_panorama(const frm_ctx* ctx, uint32_t* out_face_size);
 /* Reassemble a frame from per-rank band buffers laid out rank-major in dev_src
  * (rank r's buffer starts at r*rank_stride_bytes, as written by frm_render_bands with
  * first_band = r, band_stride = ranks) into row-major dev_dst. Asynchronous. */
