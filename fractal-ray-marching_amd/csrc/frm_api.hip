@@ -50,6 +50,24 @@ int not_panorama(frm_ctx* ctx, const char* what) {
               what);
 }
 
+int not_dof(frm_ctx* ctx, const char* what) {
+  return fail(ctx, FRM_ERR_UNSUPPORTED,
+              "%s: not available on a depth-of-field context (frm_set_depth_of_field); switch that off, or render "
+              "on a plain context and call frm_depth_of_field",
+              what);
+}
+
+// The lens of frm_dof_coc, frm_depth_of_field and frm_set_depth_of_field.
+int check_lens(frm_ctx* ctx, float aperture, float focus, uint32_t max_radius) {
+  if (max_radius > FRM_MAX_DOF_RADIUS)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "depth-of-field radius %u above %u", max_radius, FRM_MAX_DOF_RADIUS);
+  if (!(aperture >= 0.0f) || aperture > 3.402823466e+38f)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "depth-of-field aperture %g: not finite or negative", (double)aperture);
+  if (!(focus > 0.0f) || focus > 3.402823466e+38f)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "depth-of-field focus %g: not finite and positive", (double)focus);
+  return FRM_OK;
+}
+
 // The fractal loop work a frame's parameters ask for (include/frm.h FRM_MAX_NUM_ITERATIONS):
 // trips of the DE's loop per evaluation, after the reference's own loop semantics
 // (Sierpinski's i32 loop runs none for N >= 2^31: compute_scene_uniforms sets n = 0).
@@ -245,7 +263,7 @@ int frm_destroy(frm_ctx* ctx) {
     // pool blocks back to the pool (every stream is idle), then the pool itself below
     if (ctx->stream) {
       for (const PoolBuf* b : {&sl.fbs[0], &sl.fbs[1], &sl.res[0], &sl.res[1], &sl.refine_list, &sl.records, &sl.present_dev,
-                               &sl.shutter_src, &sl.shutter_acc, &sl.pano_src, &sl.pano_tables})
+                               &sl.shutter_src, &sl.shutter_acc, &sl.pano_src, &sl.pano_tables, &sl.depth})
         if (b->p) (void)hipFreeAsync(b->p, ctx->stream);
       for (void* b : {(void*)sl.refine_ctl, (void*)sl.sched_iota, (void*)sl.sched_order, (void*)sl.sched_keys, sl.sched_temp})
         if (b) (void)hipFreeAsync(b, ctx->stream);
@@ -299,7 +317,7 @@ static int resize_render(frm_ctx* ctx, uint32_t width, uint32_t height) {
   ctx->width = width;
   ctx->height = height;
   ctx->last_slot = 0;
-  for (Slot& sl : ctx->slots) sl.adaptive[0] = sl.adaptive[1] = false;  // adaptive frames of the old size
+  for (Slot& sl : ctx->slots) sl.adaptive[0] = sl.adaptive[1] = sl.dof[0] = sl.dof[1] = false;  // second images of the old size
   // no frame of the new size yet: frm_read_frame_async / frm_present_async refuse until the next
   // frm_render (tickets issued before keep their frames)
   ctx->render_seq = 0;
@@ -363,6 +381,11 @@ int frm_set_supersampling(frm_ctx* ctx, uint32_t factor) {
   if (factor == 0 || factor > FRM_MAX_SUPERSAMPLE)
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "supersampling factor %u outside [1, %u]; factor not changed", factor,
                 FRM_MAX_SUPERSAMPLE);
+  if (factor > 1u && ctx->dof_radius)
+    return fail(ctx, FRM_ERR_UNSUPPORTED,
+                "supersampling factor %u on a depth-of-field context (frm_set_depth_of_field): switch that off "
+                "first; factor not changed",
+                factor);
   if (factor > 1u && ctx->panorama)
     return fail(ctx, FRM_ERR_UNSUPPORTED,
                 "supersampling factor %u on a panorama context (frm_set_panorama): switch that off first; "
@@ -425,6 +448,11 @@ int frm_set_adaptive(frm_ctx* ctx, uint32_t factor, uint32_t threshold) {
                 "adaptive factor %u: the %ux%u frame's samples would lie on a frame above %u texels a side; values "
                 "not changed",
                 factor, ctx->out_width, ctx->out_height, FRM_MAX_DIMENSION);
+  if (factor > 1u && ctx->dof_radius)
+    return fail(ctx, FRM_ERR_UNSUPPORTED,
+                "adaptive factor %u on a depth-of-field context (frm_set_depth_of_field): switch that off first; "
+                "values not changed",
+                factor);
   if (factor > 1u && ctx->panorama)
     return fail(ctx, FRM_ERR_UNSUPPORTED,
                 "adaptive factor %u on a panorama context (frm_set_panorama): switch that off first; values "
@@ -736,6 +764,9 @@ int frm_reload(frm_ctx* ctx, const char* source_dir) {
   ReloadedKernels* rk[FRM_MAX_DEVICES] = {};
   if (source_dir && ctx->adaptive > 1u)  // the refine kernel is not part of the runtime-compiled source
     return fail(ctx, FRM_ERR_UNSUPPORTED, "frm_reload on an adaptive context (frm_set_adaptive); previous kernels kept");
+  if (source_dir && ctx->dof_radius)  // the depth pass reads the built-in kernels' records
+    return fail(ctx, FRM_ERR_UNSUPPORTED,
+                "frm_reload on a depth-of-field context (frm_set_depth_of_field); previous kernels kept");
   if (source_dir)
     for (uint32_t r = 0; r < n; ++r) {
       std::string log;
@@ -798,6 +829,7 @@ int frm_render_bands(frm_ctx* ctx, uint8_t* dev_dst, size_t dst_bytes, uint32_t 
   if (ctx->supersample > 1u) return not_supersampled(ctx, "frm_render_bands");
   if (ctx->adaptive > 1u) return not_adaptive(ctx, "frm_render_bands");
   if (ctx->panorama) return not_panorama(ctx, "frm_render_bands");
+  if (ctx->dof_radius) return not_dof(ctx, "frm_render_bands");
   if (!dev_dst || band_rows == 0 || band_stride == 0)
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "invalid dst or band geometry");
   uint32_t rows = band_local_rows(ctx->height, band_rows, first_band, band_stride);
@@ -866,6 +898,7 @@ int frm_render_bands_batch(frm_ctx* ctx, uint32_t count, const frm_parameters* p
   if (ctx->supersample > 1u) return not_supersampled(ctx, "frm_render_bands_batch");
   if (ctx->adaptive > 1u) return not_adaptive(ctx, "frm_render_bands_batch");
   if (ctx->panorama) return not_panorama(ctx, "frm_render_bands_batch");
+  if (ctx->dof_radius) return not_dof(ctx, "frm_render_bands_batch");
   if (!ctx->width) return fail(ctx, FRM_ERR_NOT_READY, "frm_resize has not been called");
   if (!params || !dev_dst || count == 0 || count > FRM_MAX_BATCH || band_rows == 0 || band_stride == 0)
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "invalid batch (count %u, at most %u) or band geometry", count,
@@ -943,6 +976,7 @@ int frm_render_shutter(frm_ctx* ctx, uint32_t count, const frm_parameters* param
   if (ctx->adaptive > 1u)
     return fail(ctx, FRM_ERR_UNSUPPORTED, "frm_render_shutter: not available on an adaptive context (frm_set_adaptive)");
   if (ctx->panorama) return not_panorama(ctx, "frm_render_shutter");
+  if (ctx->dof_radius) return not_dof(ctx, "frm_render_shutter");
   if (!ctx->width) return fail(ctx, FRM_ERR_NOT_READY, "frm_resize has not been called");
   for (uint32_t k = 0; k < count; ++k) {
     SceneUniforms sk;
@@ -969,7 +1003,7 @@ int frm_render_shutter(frm_ctx* ctx, uint32_t count, const frm_parameters* param
   const size_t sub_bytes = (size_t)ctx->width * ctx->height * 4u, npix_out = (size_t)ctx->out_width * ctx->out_height;
   const bool carried = chunk < count;  // several chunks: their sums go through the slot's accumulator
   if ((rc = ensure_shutter(ctx, *sl, chunk * sub_bytes, carried ? npix_out * sizeof(float4) : 0))) return rc;
-  sl->adaptive[sl->fb_idx] = false;
+  sl->adaptive[sl->fb_idx] = sl->dof[sl->fb_idx] = false;
   uint8_t* frame = sl->fb();  // what shown() reads of the slot
   if (S > 1u) {
     if ((rc = ensure_res(ctx, *sl, npix_out * 4u))) return rc;
@@ -1076,7 +1110,7 @@ static int render_panorama(frm_ctx* ctx, frm_stats* stats) {
   if ((rc = ensure_fb(ctx, *sl, (size_t)ctx->out_width * ctx->out_height * 4u)) ||
       (rc = ensure_panorama(ctx, *sl, 6u * face_bytes, ctx->out_width, ctx->out_height)))
     return rc;
-  sl->adaptive[sl->fb_idx] = false;
+  sl->adaptive[sl->fb_idx] = sl->dof[sl->fb_idx] = false;
   if (stats && (rc = stats_begin(ctx, s))) return rc;
   // the faces differ in their cameras alone (frm_panorama_parameters)
   SceneUniforms s0;
@@ -1117,6 +1151,7 @@ int frm_set_panorama(frm_ctx* ctx, uint32_t face_size) {
     if (ctx->group) return not_on_group(ctx, "frm_set_panorama");
     if (ctx->supersample > 1u) return not_supersampled(ctx, "frm_set_panorama");
     if (ctx->adaptive > 1u) return not_adaptive(ctx, "frm_set_panorama");
+    if (ctx->dof_radius) return not_dof(ctx, "frm_set_panorama");
     // the six faces are one batch in one scratch: 1 GiB of it at most, and a shared launch's u32
     // fetch positions (frm_render_bands_batch)
     const uint64_t m = (uint64_t)face_size + 2u, npix = 6u * m * m;
@@ -1213,6 +1248,82 @@ int frm_project_equirect(frm_ctx* ctx, const uint8_t* dev_faces, size_t faces_by
   return r1;
 }
 
+int frm_dof_coc(float aperture, float focus, uint32_t max_radius, const float* depth, size_t n, float* out_c) {
+  if (!depth || !out_c) return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "depth/out_c is NULL");
+  if (int rc = check_lens(nullptr, aperture, focus, max_radius)) return rc;
+  dof_coc_host(aperture, focus, max_radius, depth, n, out_c);
+  return FRM_OK;
+}
+
+int frm_depth_of_field(frm_ctx* ctx, const uint8_t* dev_src, size_t src_bytes, const float* dev_depth,
+                       size_t depth_bytes, uint32_t width, uint32_t height, float aperture, float focus,
+                       uint32_t max_radius, uint8_t* dev_dst, size_t dst_bytes, void* stream) {
+  if (!ctx || !dev_src || !dev_depth || !dev_dst)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "ctx/dev_src/dev_depth/dev_dst is NULL");
+  if (width == 0 || height == 0 || width > FRM_MAX_DIMENSION || height > FRM_MAX_DIMENSION)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "frame size %ux%u outside [1, %u]^2", width, height, FRM_MAX_DIMENSION);
+  if (int rc = check_lens(ctx, aperture, focus, max_radius)) return rc;
+  const size_t need = (size_t)width * height * 4u;  // of each of the three
+  if (int rc = check_src_dst(ctx, dev_src, src_bytes, width, height, dev_dst, dst_bytes, need, "frame")) return rc;
+  const uintptr_t za = reinterpret_cast<uintptr_t>(dev_depth), da = reinterpret_cast<uintptr_t>(dev_dst);
+  if (za % 4u) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "dev_depth not 4-byte aligned");
+  if (depth_bytes < need)
+    return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "depth holds %zu bytes, %ux%u floats need %zu", depth_bytes, width, height,
+                need);
+  if (za < da + need && da < za + need) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "dev_depth and dev_dst overlap");
+  FRM_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = ring_leave(ctx)) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  FRM_HIP(ctx, launch_dof(dev_src, dev_depth, dev_dst, width, height, aperture, focus, max_radius, s));
+  return FRM_OK;
+}
+
+int frm_set_depth_of_field(frm_ctx* ctx, float aperture, float focus, uint32_t max_radius) {
+  if (!ctx) return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (max_radius) {
+    if (int rc = check_lens(ctx, aperture, focus, max_radius)) return rc;
+    if (ctx->group) return not_on_group(ctx, "frm_set_depth_of_field");
+    if (ctx->supersample > 1u) return not_supersampled(ctx, "frm_set_depth_of_field");
+    if (ctx->adaptive > 1u) return not_adaptive(ctx, "frm_set_depth_of_field");
+    if (ctx->panorama) return not_panorama(ctx, "frm_set_depth_of_field");
+    if (ctx->flags & FRM_FLAG_SIMPLE_KERNEL)
+      return fail(ctx, FRM_ERR_UNSUPPORTED,
+                  "frm_set_depth_of_field: the depth plane comes from the persistent kernel's records; not available "
+                  "with FRM_FLAG_SIMPLE_KERNEL");
+    if (ctx->reloaded)
+      return fail(ctx, FRM_ERR_UNSUPPORTED,
+                  "frm_set_depth_of_field with runtime-reloaded kernels (frm_reload): the depth pass reads the built-in "
+                  "kernels' records");
+  }
+  const bool same_bits = memcmp(&aperture, &ctx->dof_aperture, sizeof(float)) == 0 &&
+                         memcmp(&focus, &ctx->dof_focus, sizeof(float)) == 0;
+  if (max_radius == ctx->dof_radius && (same_bits || max_radius == 0)) {
+    ctx->dof_aperture = aperture;
+    ctx->dof_focus = focus;
+    return FRM_OK;
+  }
+  // No drain: frames in flight and their tickets keep their bytes; like a size change, there is no
+  // frame under the new setting for the async readbacks until the next frm_render.
+  if (ctx->width) {
+    FRM_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = ring_leave(ctx)) return rc;
+  }
+  ctx->dof_radius = max_radius;
+  ctx->dof_aperture = aperture;
+  ctx->dof_focus = focus;
+  ctx->render_seq = 0;
+  return FRM_OK;
+}
+
+int frm_get_depth_of_field(const frm_ctx* ctx, float* out_aperture, float* out_focus, uint32_t* out_max_radius) {
+  if (!ctx || !out_aperture || !out_focus || !out_max_radius)
+    return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "ctx/out_aperture/out_focus/out_max_radius is NULL");
+  *out_aperture = ctx->dof_aperture;
+  *out_focus = ctx->dof_focus;
+  *out_max_radius = ctx->dof_radius;
+  return FRM_OK;
+}
+
 int frm_unshuffle_bands(frm_ctx* ctx, const uint8_t* dev_src, size_t rank_stride_bytes, uint8_t* dev_dst,
                         size_t dst_bytes, uint32_t band_rows, uint32_t ranks, void* stream) {
   if (!ctx || !dev_src || !dev_dst || band_rows == 0 || ranks == 0)
@@ -1220,6 +1331,7 @@ int frm_unshuffle_bands(frm_ctx* ctx, const uint8_t* dev_src, size_t rank_stride
   if (ctx->supersample > 1u) return not_supersampled(ctx, "frm_unshuffle_bands");
   if (ctx->adaptive > 1u) return not_adaptive(ctx, "frm_unshuffle_bands");
   if (ctx->panorama) return not_panorama(ctx, "frm_unshuffle_bands");
+  if (ctx->dof_radius) return not_dof(ctx, "frm_unshuffle_bands");
   if (!ctx->width) return fail(ctx, FRM_ERR_NOT_READY, "frm_resize has not been called");
   size_t need = (size_t)ctx->width * ctx->height * 4u;
   if (dst_bytes < need)
@@ -1333,6 +1445,46 @@ int frm_debug_trace(frm_ctx* ctx, float* out, size_t n_floats) {
   if (e == hipSuccess) e = hipStreamSynchronize(sl.stream);
   (void)hipFree(d);
   if (e != hipSuccess) return hip_fail(ctx, e, "frm_debug_trace");
+  return FRM_OK;
+}
+
+// the depth plane of the last frm_render (frm_debug_trace's conditions): the plane its gather used
+// on a depth-of-field context, else depth_pass over the records now
+int frm_read_depth(frm_ctx* ctx, float* dst, size_t n_floats) {
+  int rc = ensure_ready(ctx);
+  if (rc) return rc;
+  if (ctx->group) return not_on_group(ctx, "frm_read_depth");
+  if ((rc = ring_leave(ctx))) return rc;
+  if (!dst) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "dst is NULL");
+  const size_t npix = (size_t)ctx->width * ctx->height;
+  if (n_floats < npix)
+    return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "dst holds %zu floats, the depth plane needs %zu", n_floats, npix);
+  const Slot& sl = ctx->slots[ctx->last_slot];
+  if (ctx->render_seq && ctx->shutter_seq == ctx->render_seq && !ctx->last_is_ring)
+    return fail(ctx, FRM_ERR_NOT_READY, "the last frame was a frm_render_shutter frame: no single frame's depth");
+  if (ctx->render_seq && ctx->panorama_seq == ctx->render_seq && !ctx->last_is_ring)
+    return fail(ctx, FRM_ERR_NOT_READY, "the last frame was a panorama (frm_set_panorama): no single frame's depth");
+  if (!ctx->render_seq || sl.seq != ctx->render_seq)
+    return fail(ctx, FRM_ERR_NOT_READY, "no frm_render, or a later launch reused its slot's records");
+  if (!sl.records.p || sl.records.cap < npix * kRecordBytes || !sl.sched_whole || sl.sched_w != ctx->width || sl.sched_h != ctx->height)
+    return fail(ctx, FRM_ERR_NOT_READY, "the last frm_render was not a persistent launch of this frame size");
+  FRM_HIP(ctx, hipSetDevice(ctx->device));
+  hipError_t e = hipSuccess;
+  if (sl.dof[sl.fb_idx] && sl.depth.p && sl.depth_w == ctx->width && sl.depth_h == ctx->height) {
+    e = hipMemcpyAsync(dst, sl.depth.p, npix * sizeof(float), hipMemcpyDeviceToHost, sl.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(sl.stream);
+  } else {
+    // the plane is scratch of the call, from the context's pool in the order of the slot's stream: no
+    // device-wide synchronisation, frames in flight on other slots go on
+    float* d = nullptr;
+    if ((rc = dev_alloc(ctx, (void**)&d, npix * sizeof(float), sl.stream))) return rc;
+    e = launch_depth(reinterpret_cast<const ShadeGeom*>(sl.records.p), record_tails(sl.records), d, (uint32_t)npix, sl.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dst, d, npix * sizeof(float), hipMemcpyDeviceToHost, sl.stream);
+    const int r1 = dev_release(ctx, d, sl.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(sl.stream);
+    if (e == hipSuccess && r1) return r1;
+  }
+  if (e != hipSuccess) return hip_fail(ctx, e, "frm_read_depth");
   return FRM_OK;
 }
 

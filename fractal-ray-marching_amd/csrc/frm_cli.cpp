@@ -11,6 +11,14 @@
 //              [--lock-yaw 0..4] [--lock-pitch] [--time-factor X] [--gpus N] [--batch B]
 //              [--ssaa K] [--adaptive S] [--edge-threshold T] [--shutter-samples T] [--shutter F]
 //              [--panorama] [--face-size N]
+//              [--dof-aperture A --dof-focus F [--dof-radius R]] [--depth-out file.pfm]
+// With --dof-aperture A and --dof-focus F every frame is blurred by a thin lens
+// (frm_set_depth_of_field): A is the blur radius, in pixels, of a point at infinity, F the ray
+// distance in focus, R (--dof-radius, 1..16, default 16) the largest radius. Works with --frames /
+// --orbit / --out pattern; not with --ssaa, --adaptive, --shutter-samples, --panorama, --batch or
+// --gpus. --depth-out writes the last frame's depth plane (frm_read_depth: the primary hit distance,
+// +inf for a miss) as a little-endian single-channel PFM, bottom row first as the format has it; it
+// needs a single-GPU run whose frames are plain or depth-of-field frames on the persistent kernel.
 // With --panorama every frame is a 360-degree equirectangular one around the camera
 // (frm_set_panorama): --width / --height are the panorama's size, the six cube faces have N texels
 // a side (--face-size, default frm_panorama_face_size(W) = ceil(W / 4)) and the JSON lines count all
@@ -168,6 +176,10 @@ int main(int argc, char** argv) {
   float shutter = 0.5f;          // the fraction of dt they span
   bool panorama = false;
   uint32_t face_size = 0;  // 0: frm_panorama_face_size(width)
+  float dof_aperture = 0.0f, dof_focus = 0.0f;
+  uint32_t dof_radius = FRM_MAX_DOF_RADIUS;
+  bool dof_aperture_given = false, dof_focus_given = false, dof_radius_given = false;
+  const char* depth_out = nullptr;
   for (int i = 1; i < argc; ++i) {
     const char* a = argv[i];
     auto next = [&](void) -> const char* {
@@ -250,7 +262,50 @@ int main(int argc, char** argv) {
       }
       face_size = (uint32_t)k;
     }
+    else if (!strcmp(a, "--dof-aperture") || !strcmp(a, "--dof-focus")) {
+      const bool foc = a[6] == 'f';
+      const char* v = next();
+      char* end = nullptr;
+      const float x = strtof(v, &end);
+      if (end == v || *end || !(foc ? x > 0.0f : x >= 0.0f) || x > 3.402823466e+38f) {
+        fprintf(stderr, "frm_render: %s %s: not a finite %s number\n", a, v, foc ? "positive" : "non-negative");
+        return 2;
+      }
+      (foc ? dof_focus : dof_aperture) = x;
+      (foc ? dof_focus_given : dof_aperture_given) = true;
+    }
+    else if (!strcmp(a, "--dof-radius")) {
+      const char* v = next();
+      char* end = nullptr;
+      const long k = strtol(v, &end, 10);
+      if (end == v || *end || k < 1 || k > (long)FRM_MAX_DOF_RADIUS) {
+        fprintf(stderr, "frm_render: --dof-radius %s outside [1, %u]\n", v, FRM_MAX_DOF_RADIUS);
+        return 2;
+      }
+      dof_radius = (uint32_t)k;
+      dof_radius_given = true;
+    }
+    else if (!strcmp(a, "--depth-out")) depth_out = next();
     else { fprintf(stderr, "unknown argument %s\n", a); return 2; }
+  }
+  const bool dof = dof_aperture_given || dof_focus_given || dof_radius_given;
+  if (dof && !(dof_aperture_given && dof_focus_given)) {
+    fprintf(stderr, "frm_render: depth of field needs both --dof-aperture and --dof-focus\n");
+    return 2;
+  }
+  if (dof && (ssaa_given || adaptive_given || shutter_samples > 1 || panorama || batch > 1 || gpus > 0)) {
+    fprintf(stderr, "frm_render: --dof-* excludes --ssaa, --adaptive, --shutter-samples, --panorama, --batch and --gpus "
+                    "(the gather works on one plain frame and its depth)\n");
+    return 2;
+  }
+  if (dof && (flags & FRM_FLAG_SIMPLE_KERNEL)) {
+    fprintf(stderr, "frm_render: --dof-* excludes --simple (the depth plane comes from the persistent kernel)\n");
+    return 2;
+  }
+  if (depth_out && (batch > 1 || gpus > 0 || panorama || shutter_samples > 1)) {
+    fprintf(stderr, "frm_render: --depth-out excludes --batch, --gpus, --panorama and --shutter-samples (no single "
+                    "frame's depth)\n");
+    return 2;
   }
   if (face_size && !panorama) {
     fprintf(stderr, "frm_render: --face-size needs --panorama\n");
@@ -314,6 +369,7 @@ int main(int argc, char** argv) {
     check(frm_resize(ctx, width, height), ctx, "frm_resize");
     check(frm_set_adaptive(ctx, adaptive, edge_threshold), ctx, "frm_set_adaptive");
     if (panorama) check(frm_set_panorama(ctx, face_size), ctx, "frm_set_panorama");
+    if (dof) check(frm_set_depth_of_field(ctx, dof_aperture, dof_focus, dof_radius), ctx, "frm_set_depth_of_field");
   }
   std::vector<uint8_t> rgba((size_t)width * height * 4);
   if (batch < 1 || batch > FRM_MAX_BATCH) {
@@ -355,12 +411,24 @@ int main(int argc, char** argv) {
            "\"pos\": [%.5f, %.5f, %.5f], \"yaw\": %.5f, \"pitch\": %.5f, \"kernel_ms\": %.3f, "
            "\"march_steps\": %llu, \"hit_pixels\": %llu, \"gsteps_per_s\": %.3f, \"ssaa\": %u, "
            "\"adaptive\": %u, \"edge_threshold\": %u, \"refined_pixels\": %llu, \"shutter_samples\": %u, "
-           "\"shutter\": %.6f, \"panorama\": %u, \"face_size\": %u}\n",
+           "\"shutter\": %.6f, \"panorama\": %u, \"face_size\": %u, \"dof_aperture\": %.6f, "
+           "\"dof_focus\": %.6f, \"dof_radius\": %u}\n",
            fr, name, width, height, p.time, cam.position[0], cam.position[1], cam.position[2], cam.yaw,
            cam.pitch, st.kernel_ms, (unsigned long long)st.march_steps, (unsigned long long)st.hit_pixels,
            st.march_steps / (st.kernel_ms * 1e-3) / 1e9, ssaa, adaptive, edge_threshold,
            (unsigned long long)(adaptive > 1 ? (st.pixels - (uint64_t)width * height) / (adaptive * adaptive) : 0),
-           shutter_samples, shutter, panorama ? 1u : 0u, face_size);
+           shutter_samples, shutter, panorama ? 1u : 0u, face_size, dof ? dof_aperture : 0.0f, dof ? dof_focus : 0.0f,
+           dof ? dof_radius : 0u);
+  }
+  if (depth_out) {  // the last frame's; the render size (--ssaa: the supersampled frame's)
+    const uint32_t dw = ssaa * width, dh = ssaa * height;
+    std::vector<float> depth((size_t)dw * dh);
+    check(frm_read_depth(ctx, depth.data(), depth.size()), ctx, "frm_read_depth");
+    FILE* f = fopen(depth_out, "wb");
+    if (!f) { perror(depth_out); return 1; }
+    fprintf(f, "Pf\n%u %u\n-1.0\n", dw, dh);  // a negative scale: little-endian floats
+    for (uint32_t y = dh; y-- > 0;) fwrite(&depth[(size_t)y * dw], sizeof(float), dw, f);
+    fclose(f);
   }
   frm_destroy(ctx);
   return 0;

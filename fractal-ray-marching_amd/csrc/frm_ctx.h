@@ -93,6 +93,12 @@ struct Slot {
   // (equirect_tables) of a pano_w x pano_h output, uploaded when the output size changes
   PoolBuf pano_src, pano_tables;
   uint32_t pano_w = 0, pano_h = 0;
+  // depth of field (frm_set_depth_of_field): res[i] holds the gathered frame of fbs[i] (dof[i]: the
+  // slot's last frm_render into fbs[i] was gathered) and `depth` the plane of the slot's last such
+  // frame, depth_w x depth_h floats (frm_read_depth)
+  bool dof[2] = {false, false};
+  PoolBuf depth;
+  uint32_t depth_w = 0, depth_h = 0;
   unsigned int* queue = nullptr;
   PoolBuf records;  // persistent kernel scratch (ShadeGeom[n] then ShadeTail[n], record_tails), grown on demand
   // pixel scheduling state (frm_sched.hip), sched_cap entries each: 0..cap-1, the fetch
@@ -250,6 +256,8 @@ struct frm_ctx {
   uint64_t shutter_seq = 0;  // render_seq of the last frm_render_shutter (0: none)
   uint32_t panorama = 0;      // frm_set_panorama: the face size N (0: off); the render size is (N + 2)^2
   uint64_t panorama_seq = 0;  // render_seq of the last panorama frm_render (0: none)
+  uint32_t dof_radius = 0;  // frm_set_depth_of_field: the largest radius R (0: off)
+  float dof_aperture = 0.0f, dof_focus = 1.0f;
   // host copies of direction tables whose upload may still be running: each is released once the
   // event recorded after its copy has completed (upload_tables), the rest by frm_destroy
   struct HostBlock {

@@ -6,6 +6,7 @@
 
 #include "frm.h"
 #include "frm_uniforms.h"
+#include "frm_dof_kernels.h"
 
 using namespace frm;
 
@@ -415,5 +416,13 @@ void equirect_tables(uint32_t w, uint32_t h, float* out) {
     lat_t[y] = (float)sin(lat);
     lat_t[h + y] = (float)cos(lat);
   }
+}
+}  // namespace frm
+
+// ---- depth of field (frm.h "depth of field") -------------------------------------------------
+namespace frm {
+void dof_coc_host(float aperture, float focus, uint32_t max_radius, const float* depth, size_t n, float* out_c) {
+  const float rf = (float)max_radius;
+  for (size_t i = 0; i < n; ++i) out_c[i] = dof_coc(aperture, focus, rf, depth[i]);
 }
 }  // namespace frm

@@ -262,6 +262,13 @@ hipError_t launch_shutter(const uint8_t* src, size_t frame_stride_bytes, uint32_
 // in device memory.
 hipError_t launch_project_equirect(const uint8_t* faces, size_t face_stride_bytes, uint32_t n, const float* tables,
                                    uint8_t* dst, uint32_t dw, uint32_t dh, hipStream_t stream);
+// Depth of field (frm_set_depth_of_field, frm_depth_of_field, frm_read_depth; frm_dof_kernels.h).
+// launch_depth: z[i] = geom[i].t where tails[i] has kRecHit, +inf elsewhere, for i < npix.
+// launch_dof: dst = the gather of src (height rows of width RGBA8 sRGB texels) by depth (as many
+// floats); all 4-byte aligned, dst overlapping neither; radius <= FRM_MAX_DOF_RADIUS.
+hipError_t launch_depth(const ShadeGeom* geom, const ShadeTail* tails, float* z, uint32_t npix, hipStream_t stream);
+hipError_t launch_dof(const uint8_t* src, const float* depth, uint8_t* dst, uint32_t width, uint32_t height,
+                      float aperture, float focus, uint32_t radius, hipStream_t stream);
 // Adaptive supersampling (frm_set_adaptive, frm_refine; frm_refine_kernels.h): dst = src with alpha
 // 255 (height rows of width RGBA8 sRGB texels, both 4-byte aligned, not overlapping), except the
 // pixels whose 3 x 3 neighbourhood in src has a contrast >= threshold: those are the box resolve

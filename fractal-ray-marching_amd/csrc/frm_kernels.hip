@@ -13,6 +13,7 @@
 #include "frm_refine_kernels.h"
 #include "frm_shutter_kernels.h"
 #include "frm_panorama_kernels.h"
+#include "frm_dof_kernels.h"
 
 namespace frm {
 

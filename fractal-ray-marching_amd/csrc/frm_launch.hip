@@ -114,15 +114,31 @@ int ensure_panorama(frm_ctx* ctx, Slot& sl, size_t src_bytes, uint32_t w, uint32
   return FRM_OK;
 }
 // The second image of the slot's current framebuffer, on the slot stream, after the frame is
-// complete there: the box resolve of a supersampled context, or the adaptive frame of an adaptive
+// complete there: the box resolve of a supersampled context, the adaptive frame of an adaptive
 // one (the edge pass over the frame, then the samples of its refined pixels; their work is added
-// to the context's counters). The slot's `done` event is recorded again, so that it covers it.
+// to the context's counters), or the gathered frame of a depth-of-field one (the depth plane of the
+// slot's records, then the gather; kernel_for has put the frame on the persistent kernel, whose
+// launch wrote the records of this slot). The slot's `done` event is recorded again, so that it
+// covers it.
 int resolve_frame(frm_ctx* ctx, Slot& sl) {
-  sl.adaptive[sl.fb_idx] = false;
-  if (ctx->supersample == 1u && ctx->adaptive == 1u) return FRM_OK;
+  sl.adaptive[sl.fb_idx] = sl.dof[sl.fb_idx] = false;
+  if (ctx->supersample == 1u && ctx->adaptive == 1u && ctx->dof_radius == 0u) return FRM_OK;
   if (int rc = ensure_res(ctx, sl, (size_t)ctx->out_width * ctx->out_height * 4u)) return rc;
   uint8_t* res = sl.res[sl.fb_idx].p;
-  if (ctx->adaptive > 1u) {  // (excludes supersampling: the render size is the output size)
+  if (ctx->dof_radius) {  // (excludes supersampling and the adaptive pass: the render size is the output size)
+    const size_t npix = (size_t)ctx->width * ctx->height;
+    if (!sl.records.p || sl.records.cap < npix * kRecordBytes)
+      return fail(ctx, FRM_ERR_HIP, "depth of field: the frame left no records in its slot");
+    sl.depth_w = sl.depth_h = 0;
+    if (int rc = pool_grow(ctx, sl.depth, npix * sizeof(float), sl.stream)) return rc;
+    FRM_HIP(ctx, launch_depth(reinterpret_cast<const ShadeGeom*>(sl.records.p), record_tails(sl.records),
+                              (float*)sl.depth.p, (uint32_t)npix, sl.stream));
+    FRM_HIP(ctx, launch_dof(sl.fb(), (const float*)sl.depth.p, res, ctx->width, ctx->height, ctx->dof_aperture,
+                            ctx->dof_focus, ctx->dof_radius, sl.stream));
+    sl.dof[sl.fb_idx] = true;
+    sl.depth_w = ctx->width;
+    sl.depth_h = ctx->height;
+  } else if (ctx->adaptive > 1u) {  // (excludes supersampling: the render size is the output size)
     if (int rc = ensure_refine(ctx, sl, (size_t)ctx->width * ctx->height)) return rc;
     FrameUniforms f;
     compute_frame_uniforms(ctx->params, ctx->adaptive * ctx->width, ctx->adaptive * ctx->height, ctx->max_steps, &f);
@@ -140,7 +156,7 @@ int resolve_frame(frm_ctx* ctx, Slot& sl) {
 }
 // What the presentation paths read of a slot: out_width x out_height texels.
 const uint8_t* shown(const frm_ctx* ctx, const Slot& sl) {
-  return ctx->supersample > 1u || sl.adaptive[sl.fb_idx] ? sl.res[sl.fb_idx].p : sl.fb();
+  return ctx->supersample > 1u || sl.adaptive[sl.fb_idx] || sl.dof[sl.fb_idx] ? sl.res[sl.fb_idx].p : sl.fb();
 }
 
 static uint32_t num_bands(uint32_t height, uint32_t band_rows) { return (height + band_rows - 1) / band_rows; }
@@ -198,6 +214,7 @@ KernelArgs make_args(const frm_ctx* ctx, const frm_parameters& params, const Sce
 KernelKind kernel_for(const frm_ctx* ctx, uint64_t pixels) {
   if (ctx->flags & FRM_FLAG_SIMPLE_KERNEL) return kKernelSimple;
   if (ctx->flags & FRM_FLAG_PERSISTENT_KERNEL) return kKernelPersistent;
+  if (ctx->dof_radius) return kKernelPersistent;  // the depth plane comes from its records (same bytes)
   return pixels < kSimplePixelsPerCu * (uint64_t)ctx->cu_count ? kKernelSimple : kKernelPersistent;
 }
 

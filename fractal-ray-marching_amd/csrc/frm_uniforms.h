@@ -25,5 +25,7 @@ void compute_frame_uniforms(const frm_parameters& p, uint32_t width, uint32_t he
                             uint32_t max_steps, FrameUniforms* f);
 uint64_t wom_ops(const SceneUniforms& u, const uint64_t* counters);
 void equirect_tables(uint32_t w, uint32_t h, float* out);  // 2*w + 2*h floats
+// out_c[i] = dof_coc of depth[i] (frm_dof_kernels.h, compiled for the host), i < n
+void dof_coc_host(float aperture, float focus, uint32_t max_radius, const float* depth, size_t n, float* out_c);
 
 }  // namespace frm

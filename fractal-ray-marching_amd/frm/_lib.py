@@ -26,6 +26,7 @@ FRM_MAX_FRAMES_IN_FLIGHT = 8
 FRM_MAX_DEVICES = 16
 FRM_MAX_BATCH = 32
 FRM_MAX_SHUTTER_SAMPLES = 32
+FRM_MAX_DOF_RADIUS = 16
 FRM_MAX_SUPERSAMPLE = 4
 FRM_ADAPTIVE_DEFAULT_THRESHOLD = 16
 FRM_DEFAULT_MAX_STEPS = 5000
@@ -202,6 +203,16 @@ SIGNATURES = [
       ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]),
     ("frm_set_panorama", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
     ("frm_get_panorama", ctypes.c_int, [ctypes.c_void_p, _P(ctypes.c_uint32)]),
+    ("frm_dof_coc", ctypes.c_int,
+     [ctypes.c_float, ctypes.c_float, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    ("frm_depth_of_field", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32,
+      ctypes.c_uint32, ctypes.c_float, ctypes.c_float, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t,
+      ctypes.c_void_p]),
+    ("frm_set_depth_of_field", ctypes.c_int, [ctypes.c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_uint32]),
+    ("frm_get_depth_of_field", ctypes.c_int,
+     [ctypes.c_void_p, _P(ctypes.c_float), _P(ctypes.c_float), _P(ctypes.c_uint32)]),
+    ("frm_read_depth", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
 ]
 
 _lib = None

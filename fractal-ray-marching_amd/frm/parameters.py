@@ -242,6 +242,18 @@ def panorama_face_size(width):
     return n.value
 
 
+def dof_coc(aperture, focus, max_radius, depth):
+    """frm_dof_coc: the circle-of-confusion radius c, in pixels, of every value of `depth` (any shape,
+    float32) under a lens of `aperture`, `focus` and largest radius `max_radius`."""
+    import numpy as np
+
+    z = np.ascontiguousarray(depth, dtype=np.float32)
+    out = np.empty_like(z)
+    _lib.check(_lib.load().frm_dof_coc(float(aperture), float(focus), int(max_radius), z.ctypes.data, z.size,
+                                       out.ctypes.data))
+    return out
+
+
 def equirect_tables(width, height):
     """frm_equirect_tables: (sin_lon[width], cos_lon[width], sin_lat[height], cos_lat[height]) float32
     arrays: the directions of a width x height equirectangular frame's columns and rows."""

@@ -12,10 +12,11 @@ from . import _lib
 
 class Renderer:
     def __init__(self, device=0, max_steps=0, flags=0, frames_in_flight=1, devices=None, supersampling=1,
-                 adaptive=None, panorama=0):
+                 adaptive=None, panorama=0, depth_of_field=None):
         """supersampling: samples per pixel and axis (frm_set_supersampling; 1 = off).
         adaptive: (S, threshold) or S: S x S samples for the pixels on an edge only (frm_set_adaptive).
         panorama: cube face size N; every frame is a 360-degree equirectangular one (frm_set_panorama; 0 = off).
+        depth_of_field: (aperture, focus, radius): every frame is blurred by a thin lens (frm_set_depth_of_field).
         devices: a list of HIP device ordinals for a GROUP context (frm_config.device_count):
         every frame is row-tiled over them and gathered on devices[0] (RCCL, or device copies
         when a device repeats); the rest of the API is the same."""
@@ -39,6 +40,7 @@ class Renderer:
         self.supersampling = 1
         self._adaptive = (1, _lib.FRM_ADAPTIVE_DEFAULT_THRESHOLD)
         self.panorama = 0
+        self._dof = (0.0, 1.0, 0)
         try:
             if supersampling != 1:
                 self.set_supersampling(supersampling)
@@ -46,6 +48,8 @@ class Renderer:
                 self.set_adaptive(*(adaptive if isinstance(adaptive, (tuple, list)) else (adaptive,)))
             if panorama:
                 self.set_panorama(panorama)
+            if depth_of_field is not None:
+                self.set_depth_of_field(*depth_of_field)
         except Exception:
             self.close()
             raise
@@ -104,6 +108,33 @@ class Renderer:
         asynchronously on `stream` (0: the context's)."""
         self._check(self._lib.frm_project_equirect(self.ctx, faces_ptr, faces_bytes, face_stride, face_size, dst_ptr,
                                                    dst_bytes, out_w, out_h, stream or None))
+
+    def set_depth_of_field(self, aperture, focus, max_radius):
+        """frm_set_depth_of_field: from the next render on, every frame is gathered in linear light by each
+        pixel's circle of confusion: `aperture` is the blur radius, in pixels, of a point at infinity,
+        `focus` the ray distance in focus, `max_radius` (0..FRM_MAX_DOF_RADIUS) the largest radius; 0
+        switches it off."""
+        self._check(self._lib.frm_set_depth_of_field(self.ctx, aperture, focus, max_radius))
+        self._dof = (float(aperture), float(focus), int(max_radius))
+
+    @property
+    def dof(self):
+        """(aperture, focus, max_radius) of frm_set_depth_of_field; max_radius 0 = off."""
+        return self._dof
+
+    def depth_of_field(self, src_ptr, src_bytes, depth_ptr, depth_bytes, width, height, aperture, focus, max_radius,
+                       dst_ptr, dst_bytes, stream=0):
+        """frm_depth_of_field: gathers the height x width RGBA8 sRGB frame at device pointer src_ptr by the
+        float32 depth plane at depth_ptr into dst_ptr, asynchronously on `stream` (0: the context's)."""
+        self._check(self._lib.frm_depth_of_field(self.ctx, src_ptr, src_bytes, depth_ptr, depth_bytes, width, height,
+                                                 aperture, focus, max_radius, dst_ptr, dst_bytes, stream or None))
+
+    def read_depth(self):
+        """frm_read_depth: the depth plane of the last render, (H, W) float32: the primary hit distance of
+        every hit pixel, +inf elsewhere."""
+        out = np.zeros((self.render_height, self.render_width), np.float32)
+        self._check(self._lib.frm_read_depth(self.ctx, out.ctypes.data, out.size))
+        return out
 
     def resolve(self, src_ptr, src_bytes, out_w, out_h, factor, dst_ptr, dst_bytes, stream=0):
         """frm_resolve: box-resolve (factor*out_h) x (factor*out_w) RGBA8 sRGB texels at device pointer

@@ -505,6 +505,82 @@ int frm_project_equirect(frm_ctx* ctx, const uint8_t* dev_faces, size_t faces_by
                          uint32_t out_height, void* stream);
 int frm_set_panorama(frm_ctx* ctx, uint32_t face_size);
 int frm_get_panorama(const frm_ctx* ctx, uint32_t* out_face_size);
+/* ---- depth of field: a depth plane and a thin-lens gather in linear light (no reference
+ *      counterpart: the reference has a pinhole camera and hands out no depth).
+ *      Inputs:
+ *        - A frame S of W x H RGBA8 sRGB texels.
+ *        - A depth plane Z of W x H f32 values.
+ *        - A, the aperture: the blur radius, in pixels, of a point at infinity. Finite, >= 0.
+ *        - F, the focus distance. Finite, > 0.
+ *        - R, the largest radius: an integer in 0..FRM_MAX_DOF_RADIUS, with FRM_MAX_DOF_RADIUS = 16.
+ *        - D, the blit's sRGB decode table.
+ *        - kPi = f32(pi).
+ *      All arithmetic is f32 with no contraction, and every division is an IEEE division.
+ *      Per pixel q (depends on q alone):
+ *          c = A * fabsf(1.0f - F / Z[q])      (thin lens; Z = +inf gives c = A; Z = 0 gives +inf, or NaN when A = 0)
+ *          if (!(c >= 0.0f)) c = 0.0f          (NaN: in focus)
+ *          if (c > (float)R) c = (float)R
+ *          a = c * c;   w = 1.0f / (kPi * a + 1.0f)
+ *      Per output pixel p: Start with sw = sr = sg = sb = 0.0f. Loop dy from -R to R, outer, top to
+ *      bottom. Loop dx from -R to R, inner, left to right. Let q = p + (dx, dy). Skip q when it lies
+ *      outside the frame: the window is clipped, not clamped.
+ *          use_p = (Z[q] > Z[p]) && (c[p] < c[q])       (a sample behind p spreads no wider than p's own circle:
+ *          a_e = use_p ? a[p] : a[q]                      no background bleeding onto a sharper foreground)
+ *          w_e = use_p ? w[p] : w[q]
+ *          if ((float)(dx*dx + dy*dy) <= a_e):
+ *              sw = sw + w_e
+ *              sr = sr + w_e * D[S[q].r]                  (one multiply, one add; likewise g, b)
+ *      Then:
+ *          out[p] = encode(sr / sw), encode(sg / sw), encode(sb / sw), 255
+ *      encode is the sRGB store. The source alpha is ignored. q = p always passes, so sw >= w[p] > 0;
+ *      adding 0.0f for a sample that does not pass gives the same bits as skipping it (the sums are
+ *      never negative); a and w are functions of one pixel. A = 0 gives c = 0 everywhere, hence
+ *      sw = 1 and the source frame's bytes with alpha 255; R = 0 does the same.
+ *      Known limits. Z is the ray distance t, not the planar depth: the focus surface is a sphere
+ *      around the camera. Taking t * dir.z instead would need the camera's normalize sequence pinned
+ *      in a second reference; it is left for later. A point behind a blurred foreground object is
+ *      not recovered: the frame holds one surface per pixel.
+ * frm_dof_coc: out_c[i] = c of depth[i] for i < n, as above (host only; the code the kernel runs,
+ *      compiled for the host). FRM_ERR_INVALID_ARGUMENT for NULL, max_radius above
+ *      FRM_MAX_DOF_RADIUS, an aperture that is not finite and >= 0 or a focus that is not finite
+ *      and > 0.
+ * frm_depth_of_field: the gather alone, on any context, asynchronous on `stream` (NULL: the
+ *      context's). dev_src and dev_dst hold height rows of width RGBA8 sRGB texels, dev_depth as many
+ *      floats, row-major. All device memory of the context's GPU, 4-byte aligned; dev_dst overlaps
+ *      neither input. FRM_ERR_INVALID_ARGUMENT for NULL, sizes outside [1, FRM_MAX_DIMENSION],
+ *      max_radius above the limit, a non-finite or negative aperture, a focus that is not finite
+ *      and positive, misalignment or overlap; FRM_ERR_BUFFER_TOO_SMALL for short buffers.
+ * frm_set_depth_of_field: switches the effect on; max_radius = 0 (the default) is off: nothing is
+ *      allocated and frm_render enqueues the launches it did before (the host tests the radius in
+ *      kernel_for and resolve_frame; that the plain frame's time is unchanged rests on bench.py's
+ *      comparison with the parent's library, DESIGN.md "Depth of field"). When on, every frm_render renders as before, always on the
+ *      persistent kernel whatever the frame's size (the bytes are the same), then turns the slot's
+ *      records into a depth plane (hit: the primary hit distance t; miss: +inf) and gathers on the
+ *      slot's stream into the slot's second image, which frm_read_frame, frm_present, their async
+ *      forms and frm_frame_pixels see. A change acts as frm_set_adaptive does: no drain, frames in
+ *      flight and their tickets keep their bytes, async readbacks give FRM_ERR_NOT_READY until the
+ *      next frm_render. frm_stats holds the plain frame's counters; kernel_ms includes both passes.
+ *      Such frames never go through the resident ring. FRM_ERR_UNSUPPORTED, with nothing changed:
+ *      max_radius >= 1 on a group, supersampled, adaptive or panorama context, on a context with
+ *      FRM_FLAG_SIMPLE_KERNEL or with runtime-reloaded kernels active; and on a depth-of-field
+ *      context frm_set_supersampling(k > 1), frm_set_adaptive(k > 1), frm_set_panorama(N >= 1),
+ *      frm_render_shutter, frm_render_bands, frm_render_bands_batch, frm_unshuffle_bands and
+ *      frm_reload(dir). FRM_ERR_INVALID_ARGUMENT (values unchanged) as for frm_dof_coc; with
+ *      max_radius = 0 the aperture and focus are stored unchecked.
+ * frm_read_depth: the depth plane of the last frm_render: width * height floats, row-major,
+ *      synchronous. Available under frm_debug_trace's conditions: a whole frame on the persistent
+ *      kernel whose slot no later launch has reused; otherwise FRM_ERR_NOT_READY.
+ *      FRM_ERR_UNSUPPORTED on a group, FRM_ERR_BUFFER_TOO_SMALL for a short dst. On a depth-of-field
+ *      context the plane is the one the gather used.
+ *      Additive: FRM_ABI_VERSION stays 5. */
+#define FRM_MAX_DOF_RADIUS 16u
+int frm_dof_coc(float aperture, float focus, uint32_t max_radius, const float* depth, size_t n, float* out_c);
+int frm_depth_of_field(frm_ctx* ctx, const uint8_t* dev_src, size_t src_bytes, const float* dev_depth,
+                       size_t depth_bytes, uint32_t width, uint32_t height, float aperture, float focus,
+                       uint32_t max_radius, uint8_t* dev_dst, size_t dst_bytes, void* stream);
+int frm_set_depth_of_field(frm_ctx* ctx, float aperture, float focus, uint32_t max_radius);
+int frm_get_depth_of_field(const frm_ctx* ctx, float* out_aperture, float* out_focus, uint32_t* out_max_radius);
+int frm_read_depth(frm_ctx* ctx, float* dst, size_t n_floats);
 /* Reassemble a frame from per-rank band buffers laid out rank-major in dev_src
  * (rank r's buffer starts at r*rank_stride_bytes, as written by frm_render_bands with
  * first_band = r, band_stride = ranks) into row-major dev_dst. Asynchronous. */
