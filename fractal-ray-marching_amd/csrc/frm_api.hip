@@ -1,5 +1,6 @@
-// frm_api.hip — the C ABI of include/frm.h: context lifetime, uniform upload, frame dispatch and
-// readback. Replaces the reference's wgpu host layer
+// frm_api.hip — the C ABI of include/frm.h: context lifetime, size and frame mode, uniform upload,
+// frm_render and its variants, readback and presentation (the stream-level stages: frm_stages.hip;
+// diagnostics: frm_debug.hip). Replaces the reference's wgpu host layer
 // (graphics.rs:25-164, persistent_graphics.rs:33-173, blit_graphics.rs:16-62).
 // Errors never cross the ABI as exceptions/aborts: every HIP failure becomes a status
 // code plus a message retrievable with frm_last_error().
@@ -23,49 +24,20 @@ int hip_fail(frm_ctx* ctx, hipError_t e, const char* what) {
   return fail(ctx, code, "%s failed: %s (%d)", what, hipGetErrorString(e), (int)e);
 }
 
-namespace {
-
 int not_on_group(frm_ctx* ctx, const char* what) {
   return fail(ctx, FRM_ERR_UNSUPPORTED, "%s: not available on a group context (frm_config.device_count)", what);
 }
 
-int not_supersampled(frm_ctx* ctx, const char* what) {
-  return fail(ctx, FRM_ERR_UNSUPPORTED,
-              "%s: not available on a supersampled context (frm_set_supersampling); render the bands at the "
-              "internal size on a plain context and call frm_resolve",
-              what);
+// `what` (an entry point) does not serve the context's frame mode.
+int refuse_mode(frm_ctx* ctx, const char* what) {
+  const ModeText& m = kModeText[frame_mode(ctx)];
+  return fail(ctx, FRM_ERR_UNSUPPORTED, "%s: not available on a %s context (%s); %s; nothing changed", what, m.noun,
+              m.setter, m.instead);
 }
-
-int not_adaptive(frm_ctx* ctx, const char* what) {
-  return fail(ctx, FRM_ERR_UNSUPPORTED,
-              "%s: not available on an adaptive context (frm_set_adaptive); render the bands on a plain "
-              "context and call frm_refine",
-              what);
-}
-
-int not_panorama(frm_ctx* ctx, const char* what) {
-  return fail(ctx, FRM_ERR_UNSUPPORTED,
-              "%s: not available on a panorama context (frm_set_panorama); render the faces "
-              "(frm_panorama_parameters) on a plain context and call frm_project_equirect",
-              what);
-}
-
-int not_dof(frm_ctx* ctx, const char* what) {
-  return fail(ctx, FRM_ERR_UNSUPPORTED,
-              "%s: not available on a depth-of-field context (frm_set_depth_of_field); switch that off, or render "
-              "on a plain context and call frm_depth_of_field",
-              what);
-}
-
-// The lens of frm_dof_coc, frm_depth_of_field and frm_set_depth_of_field.
-int check_lens(frm_ctx* ctx, float aperture, float focus, uint32_t max_radius) {
-  if (max_radius > FRM_MAX_DOF_RADIUS)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "depth-of-field radius %u above %u", max_radius, FRM_MAX_DOF_RADIUS);
-  if (!(aperture >= 0.0f) || aperture > 3.402823466e+38f)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "depth-of-field aperture %g: not finite or negative", (double)aperture);
-  if (!(focus > 0.0f) || focus > 3.402823466e+38f)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "depth-of-field focus %g: not finite and positive", (double)focus);
-  return FRM_OK;
+// Whether a frame mode other than `mine` is on (a setter's question).
+static bool other_mode(const frm_ctx* ctx, FrameMode mine) {
+  const FrameMode m = frame_mode(ctx);
+  return m != kPlain && m != mine;
 }
 
 // The fractal loop work a frame's parameters ask for (include/frm.h FRM_MAX_NUM_ITERATIONS):
@@ -93,35 +65,7 @@ int ensure_ready(frm_ctx* ctx) {
   return FRM_OK;
 }
 
-// The device source (src_w x src_h texels) and destination (dst_need bytes: "the `noun`") of
-// frm_resolve, frm_refine and frm_blit, after their NULL checks: 4-byte aligned (frm_refine's
-// counters, when given, 8-byte), large enough, not overlapping, reported in this order.
-int check_src_dst(frm_ctx* ctx, const uint8_t* dev_src, size_t src_bytes, uint32_t src_w, uint32_t src_h,
-                  const uint8_t* dev_dst, size_t dst_bytes, size_t dst_need, const char* noun,
-                  const uint64_t* dev_counters = nullptr) {
-  const uintptr_t sa = reinterpret_cast<uintptr_t>(dev_src), da = reinterpret_cast<uintptr_t>(dev_dst);
-  if (sa % 4u || da % 4u) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "dev_src / dev_dst not 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(dev_counters) % 8u)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "dev_counters not 8-byte aligned");
-  const size_t src_need = (size_t)src_w * src_h * 4u;
-  if (src_bytes < src_need)
-    return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "src holds %zu bytes, %ux%u texels need %zu", src_bytes, src_w, src_h,
-                src_need);
-  if (dst_bytes < dst_need)
-    return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "dst holds %zu bytes, the %s needs %zu", dst_bytes, noun, dst_need);
-  if (sa < da + dst_need && da < sa + src_need)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "dev_src and dev_dst overlap");
-  return FRM_OK;
-}
-
-// The output size and blit flags of frm_present, frm_present_async and frm_blit; size_fmt: the
-// caller's message for a bad size (width, height, FRM_MAX_DIMENSION).
-int check_output(frm_ctx* ctx, uint32_t out_width, uint32_t out_height, uint32_t flags, const char* size_fmt) {
-  if (out_width == 0 || out_height == 0 || out_width > FRM_MAX_DIMENSION || out_height > FRM_MAX_DIMENSION)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, size_fmt, out_width, out_height, FRM_MAX_DIMENSION);
-  if (flags & ~(FRM_BLIT_SRGB | FRM_BLIT_BGRA)) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "unknown flags 0x%x", flags);
-  return FRM_OK;
-}
+namespace {
 
 // A context that failed to build: its message for frm_last_error(NULL), then released.
 int create_failed(frm_ctx* ctx, int rc) {
@@ -317,7 +261,7 @@ static int resize_render(frm_ctx* ctx, uint32_t width, uint32_t height) {
   ctx->width = width;
   ctx->height = height;
   ctx->last_slot = 0;
-  for (Slot& sl : ctx->slots) sl.adaptive[0] = sl.adaptive[1] = sl.dof[0] = sl.dof[1] = false;  // second images of the old size
+  for (Slot& sl : ctx->slots) sl.no_second(true);  // second images of the old size
   // no frame of the new size yet: frm_read_frame_async / frm_present_async refuse until the next
   // frm_render (tickets issued before keep their frames)
   ctx->render_seq = 0;
@@ -361,18 +305,14 @@ static int apply_panorama(frm_ctx* ctx, uint32_t width, uint32_t height, uint32_
 
 int frm_resize(frm_ctx* ctx, uint32_t width, uint32_t height) {
   if (!ctx) return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  if (ctx->panorama) {  // the output size is free of the render size
-    if (width == 0 || height == 0 || width > FRM_MAX_DIMENSION || height > FRM_MAX_DIMENSION)
-      return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "panorama size %ux%u outside [1, %u]^2", width, height,
-                  FRM_MAX_DIMENSION);
+  const FrameMode mode = frame_mode(ctx);
+  if (mode == kPanorama) {  // the output size is free of the render size
+    if (int rc = check_size(ctx, width, height, 1, "panorama size")) return rc;
     return apply_panorama(ctx, width, height, ctx->panorama);
   }
   // an adaptive frame's refined pixels are those of its full supersampled counterpart: the same bound
-  const uint32_t factor = ctx->adaptive > 1u ? ctx->adaptive : ctx->supersample;
-  const uint32_t limit = FRM_MAX_DIMENSION / factor;
-  if (width == 0 || height == 0 || width > limit || height > limit)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "frame size %ux%u outside [1, %u]^2 (supersampling %u)", width, height,
-                limit, factor);
+  if (int rc = check_size(ctx, width, height, mode == kAdaptive ? ctx->adaptive : ctx->supersample, "frame size"))
+    return rc;
   return apply_size(ctx, width, height, ctx->supersample);
 }
 
@@ -381,21 +321,7 @@ int frm_set_supersampling(frm_ctx* ctx, uint32_t factor) {
   if (factor == 0 || factor > FRM_MAX_SUPERSAMPLE)
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "supersampling factor %u outside [1, %u]; factor not changed", factor,
                 FRM_MAX_SUPERSAMPLE);
-  if (factor > 1u && ctx->dof_radius)
-    return fail(ctx, FRM_ERR_UNSUPPORTED,
-                "supersampling factor %u on a depth-of-field context (frm_set_depth_of_field): switch that off "
-                "first; factor not changed",
-                factor);
-  if (factor > 1u && ctx->panorama)
-    return fail(ctx, FRM_ERR_UNSUPPORTED,
-                "supersampling factor %u on a panorama context (frm_set_panorama): switch that off first; "
-                "factor not changed",
-                factor);
-  if (factor > 1u && ctx->adaptive > 1u)
-    return fail(ctx, FRM_ERR_UNSUPPORTED,
-                "supersampling factor %u on an adaptive context (frm_set_adaptive): switch that off first; "
-                "factor not changed",
-                factor);
+  if (factor > 1u && other_mode(ctx, kSupersampled)) return refuse_mode(ctx, "frm_set_supersampling");
   if (ctx->out_width) {
     const uint32_t limit = FRM_MAX_DIMENSION / factor;
     if (ctx->out_width > limit || ctx->out_height > limit)
@@ -417,25 +343,6 @@ int frm_get_supersampling(const frm_ctx* ctx, uint32_t* out_factor) {
   return FRM_OK;
 }
 
-int frm_resolve(frm_ctx* ctx, const uint8_t* dev_src, size_t src_bytes, uint32_t out_width, uint32_t out_height,
-                uint32_t factor, uint8_t* dev_dst, size_t dst_bytes, void* stream) {
-  if (!ctx || !dev_src || !dev_dst) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "ctx/dev_src/dev_dst is NULL");
-  if (factor == 0 || factor > FRM_MAX_SUPERSAMPLE)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "supersampling factor %u outside [1, %u]", factor, FRM_MAX_SUPERSAMPLE);
-  const uint32_t limit = FRM_MAX_DIMENSION / factor;
-  if (out_width == 0 || out_height == 0 || out_width > limit || out_height > limit)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "output size %ux%u outside [1, %u]^2 (factor %u)", out_width, out_height,
-                limit, factor);
-  if (int rc = check_src_dst(ctx, dev_src, src_bytes, factor * out_width, factor * out_height, dev_dst, dst_bytes,
-                             (size_t)out_width * out_height * 4u, "frame"))
-    return rc;
-  FRM_HIP(ctx, hipSetDevice(ctx->device));
-  if (int rc = ring_leave(ctx)) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  FRM_HIP(ctx, launch_resolve(dev_src, dev_dst, out_width, out_height, factor, s));
-  return FRM_OK;
-}
-
 int frm_set_adaptive(frm_ctx* ctx, uint32_t factor, uint32_t threshold) {
   if (!ctx) return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "ctx is NULL");
   if (factor == 0 || factor > FRM_MAX_SUPERSAMPLE || threshold > 256u)
@@ -448,21 +355,7 @@ int frm_set_adaptive(frm_ctx* ctx, uint32_t factor, uint32_t threshold) {
                 "adaptive factor %u: the %ux%u frame's samples would lie on a frame above %u texels a side; values "
                 "not changed",
                 factor, ctx->out_width, ctx->out_height, FRM_MAX_DIMENSION);
-  if (factor > 1u && ctx->dof_radius)
-    return fail(ctx, FRM_ERR_UNSUPPORTED,
-                "adaptive factor %u on a depth-of-field context (frm_set_depth_of_field): switch that off first; "
-                "values not changed",
-                factor);
-  if (factor > 1u && ctx->panorama)
-    return fail(ctx, FRM_ERR_UNSUPPORTED,
-                "adaptive factor %u on a panorama context (frm_set_panorama): switch that off first; values "
-                "not changed",
-                factor);
-  if (factor > 1u && ctx->supersample > 1u)
-    return fail(ctx, FRM_ERR_UNSUPPORTED,
-                "adaptive factor %u on a supersampled context (frm_set_supersampling): switch that off first; values "
-                "not changed",
-                factor);
+  if (factor > 1u && other_mode(ctx, kAdaptive)) return refuse_mode(ctx, "frm_set_adaptive");
   if (factor > 1u && ctx->reloaded)
     return fail(ctx, FRM_ERR_UNSUPPORTED,
                 "adaptive factor %u with runtime-reloaded kernels (frm_reload): the refine kernel is built in; values "
@@ -486,96 +379,6 @@ int frm_get_adaptive(const frm_ctx* ctx, uint32_t* out_factor, uint32_t* out_thr
     return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "ctx/out_factor/out_threshold is NULL");
   *out_factor = ctx->adaptive;
   *out_threshold = ctx->edge_threshold;
-  return FRM_OK;
-}
-
-int frm_refine(frm_ctx* ctx, const frm_parameters* params, const uint8_t* dev_src, size_t src_bytes, uint32_t width,
-               uint32_t height, uint32_t factor, uint32_t threshold, uint8_t* dev_dst, size_t dst_bytes,
-               uint64_t* dev_counters, void* stream) {
-  if (!ctx || !dev_src || !dev_dst) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "ctx/dev_src/dev_dst is NULL");
-  if (factor == 0 || factor > FRM_MAX_SUPERSAMPLE || threshold > 256u)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "adaptive factor %u outside [1, %u] or edge threshold %u above 256", factor,
-                FRM_MAX_SUPERSAMPLE, threshold);
-  const uint32_t limit = FRM_MAX_DIMENSION / factor;
-  if (width == 0 || height == 0 || width > limit || height > limit)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "frame size %ux%u outside [1, %u]^2 (factor %u)", width, height, limit,
-                factor);
-  const size_t need = (size_t)width * height * 4u;
-  if (int rc = check_src_dst(ctx, dev_src, src_bytes, width, height, dev_dst, dst_bytes, need, "frame", dev_counters))
-    return rc;
-  frm_parameters p;
-  SceneUniforms su;
-  if (params) {
-    p = *params;
-    compute_scene_uniforms(p, ctx->flags, &su);
-    if (int rc = check_parameters(ctx, su, p)) return rc;
-  } else {
-    if (!ctx->has_params) return fail(ctx, FRM_ERR_NOT_READY, "params is NULL and frm_set_parameters has not been called");
-    p = ctx->params;
-    su = ctx->scene;
-  }
-  FRM_HIP(ctx, hipSetDevice(ctx->device));
-  if (int rc = ring_leave(ctx)) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  // scratch per call, allocated and released in the order of the call's stream: calls in flight on
-  // different streams never share it
-  uint32_t *list = nullptr, *ctl = nullptr;
-  int rc = dev_alloc(ctx, (void**)&list, need, s);
-  if (rc) return rc;
-  if ((rc = dev_alloc(ctx, (void**)&ctl, kRefineCtlBytes, s))) {
-    (void)hipFreeAsync(list, s);
-    return rc;
-  }
-  FrameUniforms f;
-  compute_frame_uniforms(p, factor * width, factor * height, ctx->max_steps, &f);
-  const hipError_t e = launch_adaptive(f, su, dev_src, dev_dst, width, height, factor, threshold, list, ctl,
-                                       (unsigned long long*)dev_counters, ctx->cu_count, s);
-  const int r1 = dev_release(ctx, list, s), r2 = dev_release(ctx, ctl, s);
-  if (e != hipSuccess) return hip_fail(ctx, e, "launch_adaptive");
-  return r1 ? r1 : r2;
-}
-
-int frm_debug_refine_mask(frm_ctx* ctx, uint8_t* out, size_t n) {
-  if (!ctx || !out) return -fail(ctx, FRM_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (ctx->last_is_ring || !ctx->render_seq)
-    return -fail(ctx, FRM_ERR_NOT_READY, "frm_debug_refine_mask: no adaptive frm_render under the current settings");
-  const Slot& sl = ctx->slots[ctx->last_slot];
-  if (!sl.adaptive[sl.fb_idx] || sl.seq != ctx->render_seq || !sl.refine_list.p)
-    return -fail(ctx, FRM_ERR_NOT_READY, "frm_debug_refine_mask: the last frm_render was not adaptive");
-  const size_t npix = (size_t)sl.refine_w * sl.refine_h;
-  if (n > npix) n = npix;
-  if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(sl.stream) != hipSuccess)
-    return -fail(ctx, FRM_ERR_HIP, "frm_debug_refine_mask: synchronisation failed");
-  uint32_t count = 0;
-  if (hipMemcpy(&count, sl.refine_ctl, sizeof(count), hipMemcpyDeviceToHost) != hipSuccess || count > npix)
-    return -fail(ctx, FRM_ERR_HIP, "frm_debug_refine_mask: reading the list length failed");
-  uint32_t* list = new (std::nothrow) uint32_t[count ? count : 1u];
-  if (!list) return -fail(ctx, FRM_ERR_OUT_OF_MEMORY, "host allocation failed");
-  if (count && hipMemcpy(list, sl.refine_list.p, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) {
-    delete[] list;
-    return -fail(ctx, FRM_ERR_HIP, "frm_debug_refine_mask: reading the list failed");
-  }
-  memset(out, 0, n);
-  for (uint32_t k = 0; k < count; ++k)
-    if (list[k] < n) out[list[k]] = 1;
-  delete[] list;
-  return (int)n;
-}
-
-int frm_blit(frm_ctx* ctx, const uint8_t* dev_src, size_t src_bytes, uint32_t src_width, uint32_t src_height,
-             uint8_t* dev_dst, size_t dst_bytes, uint32_t out_width, uint32_t out_height, uint32_t flags, void* stream) {
-  if (!ctx || !dev_src || !dev_dst) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "ctx/dev_src/dev_dst is NULL");
-  if (src_width == 0 || src_height == 0 || src_width > FRM_MAX_DIMENSION || src_height > FRM_MAX_DIMENSION)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "source size %ux%u outside [1, %u]^2", src_width, src_height,
-                FRM_MAX_DIMENSION);
-  if (int rc = check_output(ctx, out_width, out_height, flags, "output size %ux%u outside [1, %u]^2")) return rc;
-  if (int rc = check_src_dst(ctx, dev_src, src_bytes, src_width, src_height, dev_dst, dst_bytes,
-                             (size_t)out_width * out_height * 4u, "output"))
-    return rc;
-  FRM_HIP(ctx, hipSetDevice(ctx->device));
-  if (int rc = ring_leave(ctx)) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  FRM_HIP(ctx, launch_blit(dev_src, src_width, src_height, dev_dst, out_width, out_height, flags, s));
   return FRM_OK;
 }
 
@@ -603,12 +406,9 @@ int frm_render(frm_ctx* ctx, frm_stats* stats) {
   int rc = ensure_ready(ctx);
   if (rc) return rc;
   if (ctx->group) return group_render(ctx, stats);
-  if (ctx->panorama) return render_panorama(ctx, stats);
+  if (frame_mode(ctx) == kPanorama) return render_panorama(ctx, stats);
   if (!stats && ring_eligible(ctx)) return ring_render(ctx);
-  FRM_HIP(ctx, hipSetDevice(ctx->device));
-  if ((rc = ring_quiesce(ctx))) return rc;  // a frame outside the ring: the ring's frames first
-  ctx->last_is_ring = false;
-  if (stats && (rc = synchronize_all(ctx))) return rc;  // the counters must hold this frame alone
+  if ((rc = frame_prologue(ctx, stats))) return rc;
   Slot* sl = nullptr;
   hipStream_t s;
   if ((rc = begin_frame(ctx, &sl, &s))) return rc;
@@ -618,13 +418,7 @@ int frm_render(frm_ctx* ctx, frm_stats* stats) {
   if (rc || (rc = resolve_frame(ctx, *sl))) return rc;
   show_slot(ctx, *sl);
   keep_render_params(ctx);
-  if (stats) {
-    uint64_t host[FRM_NUM_COUNTERS];
-    float ms = 0.0f;
-    if ((rc = stats_end(ctx, s, host, &ms)) || (rc = frm_stats_from_counters(ctx, host, stats))) return rc;
-    stats->kernel_ms = ms;
-  }
-  return FRM_OK;
+  return finish_stats(ctx, s, stats);
 }
 
 int frm_read_frame(frm_ctx* ctx, uint8_t* dst, size_t dst_bytes) {
@@ -645,7 +439,7 @@ int frm_present(frm_ctx* ctx, uint32_t out_width, uint32_t out_height, uint32_t 
                 size_t dst_bytes) {
   if (!ctx || !dst) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "ctx/dst is NULL");
   if (!ctx->width) return fail(ctx, FRM_ERR_NOT_READY, "frm_resize has not been called");
-  if (int rc = check_output(ctx, out_width, out_height, flags, "bad output size %ux%u")) return rc;
+  if (int rc = check_output(ctx, out_width, out_height, flags)) return rc;
   const size_t need = (size_t)out_width * out_height * 4u;
   if (dst_bytes < need)
     return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "dst holds %zu bytes, output needs %zu", dst_bytes, need);
@@ -721,7 +515,7 @@ int frm_present_async(frm_ctx* ctx, uint32_t out_width, uint32_t out_height, uin
   if (!ctx || !out_ticket) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "ctx/out_ticket is NULL");
   if (!ctx->width) return fail(ctx, FRM_ERR_NOT_READY, "frm_resize has not been called");
   if (!ctx->render_seq) return fail(ctx, FRM_ERR_NOT_READY, "no frm_render since the context was created");
-  if (int rc = check_output(ctx, out_width, out_height, flags, "bad output size %ux%u")) return rc;
+  if (int rc = check_output(ctx, out_width, out_height, flags)) return rc;
   FRM_HIP(ctx, hipSetDevice(ctx->device));
   if (int rc = ring_materialize(ctx)) return rc;
   Slot& sl = ctx->slots[ctx->last_slot];
@@ -762,11 +556,9 @@ int frm_reload(frm_ctx* ctx, const char* source_dir) {
   // a group reloads every member: all compile, or every member keeps its kernels
   const uint32_t n = ctx->group ? ctx->group->n : 1u;
   ReloadedKernels* rk[FRM_MAX_DEVICES] = {};
-  if (source_dir && ctx->adaptive > 1u)  // the refine kernel is not part of the runtime-compiled source
-    return fail(ctx, FRM_ERR_UNSUPPORTED, "frm_reload on an adaptive context (frm_set_adaptive); previous kernels kept");
-  if (source_dir && ctx->dof_radius)  // the depth pass reads the built-in kernels' records
-    return fail(ctx, FRM_ERR_UNSUPPORTED,
-                "frm_reload on a depth-of-field context (frm_set_depth_of_field); previous kernels kept");
+  // the refine kernel is not part of the runtime-compiled source; the depth pass reads the built-in kernels' records
+  const FrameMode mode = frame_mode(ctx);
+  if (source_dir && (mode == kAdaptive || mode == kDof)) return refuse_mode(ctx, "frm_reload");
   if (source_dir)
     for (uint32_t r = 0; r < n; ++r) {
       std::string log;
@@ -806,30 +598,12 @@ int frm_kernel_for_pixels(const frm_ctx* ctx, uint64_t pixels, uint32_t* out_ker
   return FRM_OK;
 }
 
-int frm_group_band_rows(uint32_t height, uint32_t devices, uint32_t* out_band_rows) {
-  if (!out_band_rows || height == 0 || devices == 0 || devices > FRM_MAX_DEVICES)
-    return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "invalid height %u or device count %u", height, devices);
-  *out_band_rows = group_band_rows(height, devices);
-  return FRM_OK;
-}
-
-int frm_band_rows_for(uint32_t height, uint32_t band_rows, uint32_t first_band, uint32_t band_stride,
-                      uint32_t* out_rows) {
-  if (!out_rows || height == 0 || band_rows == 0 || band_stride == 0)
-    return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "invalid band geometry");
-  *out_rows = band_local_rows(height, band_rows, first_band, band_stride);
-  return FRM_OK;
-}
-
 int frm_render_bands(frm_ctx* ctx, uint8_t* dev_dst, size_t dst_bytes, uint32_t band_rows,
                      uint32_t first_band, uint32_t band_stride, void* stream, uint64_t* dev_counters) {
   int rc = ensure_ready(ctx);
   if (rc) return rc;
   if (ctx->group) return not_on_group(ctx, "frm_render_bands");
-  if (ctx->supersample > 1u) return not_supersampled(ctx, "frm_render_bands");
-  if (ctx->adaptive > 1u) return not_adaptive(ctx, "frm_render_bands");
-  if (ctx->panorama) return not_panorama(ctx, "frm_render_bands");
-  if (ctx->dof_radius) return not_dof(ctx, "frm_render_bands");
+  if (frame_mode(ctx) != kPlain) return refuse_mode(ctx, "frm_render_bands");
   if (!dev_dst || band_rows == 0 || band_stride == 0)
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "invalid dst or band geometry");
   uint32_t rows = band_local_rows(ctx->height, band_rows, first_band, band_stride);
@@ -844,61 +618,13 @@ int frm_render_bands(frm_ctx* ctx, uint8_t* dev_dst, size_t dst_bytes, uint32_t 
   return launch(ctx, a, s);
 }
 
-// The frames of one multi-frame launch may differ in camera, and for the Mandelbulb in time (its
-// power, fragment.wgsl:75, is the only time-derived constant): otherwise the same scene uniforms
-// (scene, iterations, time-derived constants). Returns the first frame whose uniforms differ from
-// frame 0's in more than that (0: none); *s0: frame 0's uniforms, powers[k]: frame k's power,
-// *anim: the powers differ.
-static uint32_t batch_uniforms(const frm_ctx* ctx, uint32_t count, const frm_parameters* params, SceneUniforms* s0,
-                               float* powers, bool* anim) {
-  compute_scene_uniforms(params[0], ctx->flags, s0);
-  *anim = false;
-  powers[0] = s0->mb_power;
-  for (uint32_t k = 1; k < count; ++k) {
-    SceneUniforms sk;
-    compute_scene_uniforms(params[k], ctx->flags, &sk);
-    powers[k] = sk.mb_power;
-    if (is_mandelbulb(s0->family) && sk.family == s0->family && sk.mb_power != s0->mb_power) {
-      *anim = true;
-      sk.mb_power = s0->mb_power;
-      sk.mb_power_m1 = s0->mb_power_m1;
-    }
-    if (memcmp(s0, &sk, sizeof(sk)) != 0) return k;
-  }
-  return 0;
-}
-// Whether `count` such frames of a.npix local pixels share one launch; else one launch per frame:
-// the simple kernel has no queue to share; runtime-reloaded modules carry the single-frame kernels
-// only; per-frame powers need the Mandelbulb's N >= 1 kernels.
-static bool batch_shares_launch(const frm_ctx* ctx, const KernelArgs& a, uint32_t count, bool anim) {
-  return !(count == 1 || kernel_for(ctx, a.npix) == kKernelSimple || ctx->reloaded || (anim && a.s.n == 0));
-}
-// Makes `a` (make_args of any of the frames) the shared launch of the `count` frames, frame k written
-// frame_stride_bytes after frame k - 1.
-static void set_batch(const frm_ctx* ctx, KernelArgs& a, uint32_t count, const frm_parameters* params,
-                      const float* powers, bool anim, size_t frame_stride_bytes) {
-  a.batch = count;
-  a.out_stride = (uint32_t)(frame_stride_bytes / 4u);
-  a.anim = anim ? 1u : 0u;
-  memcpy(a.mb_powers, powers, sizeof(float) * count);
-  FrameUniforms fk;
-  for (uint32_t k = 0; k < count; ++k) {
-    compute_frame_uniforms(params[k], ctx->width, ctx->height, ctx->max_steps, &fk);
-    memcpy(a.cams[k].row, fk.row, sizeof(fk.row));
-    a.cams[k].origin = fk.origin;
-  }
-}
-
 int frm_render_bands_batch(frm_ctx* ctx, uint32_t count, const frm_parameters* params, uint8_t* dev_dst,
                            size_t dst_bytes, size_t frame_stride_bytes, uint32_t band_rows, uint32_t first_band,
                            uint32_t band_stride,
                            void* stream, uint64_t* dev_counters) {
   if (!ctx) return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "ctx is NULL");
   if (ctx->group) return not_on_group(ctx, "frm_render_bands_batch");
-  if (ctx->supersample > 1u) return not_supersampled(ctx, "frm_render_bands_batch");
-  if (ctx->adaptive > 1u) return not_adaptive(ctx, "frm_render_bands_batch");
-  if (ctx->panorama) return not_panorama(ctx, "frm_render_bands_batch");
-  if (ctx->dof_radius) return not_dof(ctx, "frm_render_bands_batch");
+  if (frame_mode(ctx) != kPlain) return refuse_mode(ctx, "frm_render_bands_batch");
   if (!ctx->width) return fail(ctx, FRM_ERR_NOT_READY, "frm_resize has not been called");
   if (!params || !dev_dst || count == 0 || count > FRM_MAX_BATCH || band_rows == 0 || band_stride == 0)
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "invalid batch (count %u, at most %u) or band geometry", count,
@@ -920,11 +646,10 @@ int frm_render_bands_batch(frm_ctx* ctx, uint32_t count, const frm_parameters* p
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "batch of %u frames of %u x %u local pixels too large", count,
                 ctx->width, rows);
   // the frames share their scene uniforms (batch_uniforms) and their aspect
-  SceneUniforms s0;
-  bool anim = false;
-  float powers[FRM_MAX_BATCH];
-  uint32_t differs = batch_uniforms(ctx, count, params, &s0, powers, &anim);
-  if (int rc = check_parameters(ctx, s0, params[0])) return rc;
+  BatchUniforms u;
+  batch_uniforms(ctx, count, params, &u);
+  if (int rc = check_parameters(ctx, u.s0, params[0])) return rc;
+  uint32_t differs = u.differs;
   for (uint32_t k = 1; k < count && (!differs || k < differs); ++k)
     if (params[k].aspect_scale[0] != params[0].aspect_scale[0] || params[k].aspect_scale[1] != params[0].aspect_scale[1])
       differs = k;
@@ -940,19 +665,8 @@ int frm_render_bands_batch(frm_ctx* ctx, uint32_t count, const frm_parameters* p
   ctx->has_params = true;
   hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
   unsigned long long* counters = dev_counters ? (unsigned long long*)dev_counters : ctx->counters;
-  KernelArgs a = make_args(ctx, ctx->params, ctx->scene, dev_dst, counters, band_rows, first_band, band_stride, rows);
-  if (!batch_shares_launch(ctx, a, count, anim)) {  // one launch per frame
-    for (uint32_t k = 0; k < count; ++k) {
-      SceneUniforms sk;
-      compute_scene_uniforms(params[k], ctx->flags, &sk);
-      a = make_args(ctx, params[k], sk, dev_dst + (size_t)k * frame_stride_bytes, counters, band_rows, first_band,
-                    band_stride, rows);
-      if (int rc = launch(ctx, a, s)) return rc;
-    }
-    return FRM_OK;
-  }
-  set_batch(ctx, a, count, params, powers, anim, frame_stride_bytes);
-  return launch(ctx, a, s);
+  return launch_frames(ctx, count, params, u, true, dev_dst, frame_stride_bytes,
+                       BandGeometry{band_rows, first_band, band_stride, rows}, counters, s, -1);
 }
 
 // Sub-frames per chunk of a shutter frame of the context's size (include/frm.h frm_render_shutter):
@@ -973,10 +687,8 @@ int frm_render_shutter(frm_ctx* ctx, uint32_t count, const frm_parameters* param
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "params is NULL or count %u outside [1, %u]", count,
                 FRM_MAX_SHUTTER_SAMPLES);
   if (ctx->group) return not_on_group(ctx, "frm_render_shutter");
-  if (ctx->adaptive > 1u)
-    return fail(ctx, FRM_ERR_UNSUPPORTED, "frm_render_shutter: not available on an adaptive context (frm_set_adaptive)");
-  if (ctx->panorama) return not_panorama(ctx, "frm_render_shutter");
-  if (ctx->dof_radius) return not_dof(ctx, "frm_render_shutter");
+  const FrameMode mode = frame_mode(ctx);  // the sub-frames of a supersampled context are resolved as they are summed
+  if (mode != kPlain && mode != kSupersampled) return refuse_mode(ctx, "frm_render_shutter");
   if (!ctx->width) return fail(ctx, FRM_ERR_NOT_READY, "frm_resize has not been called");
   for (uint32_t k = 0; k < count; ++k) {
     SceneUniforms sk;
@@ -987,11 +699,8 @@ int frm_render_shutter(frm_ctx* ctx, uint32_t count, const frm_parameters* param
       return fail(ctx, FRM_ERR_INVALID_ARGUMENT,
                   "sub-frame %u differs from sub-frame 0 in scene_index, num_iterations or aspect_scale", k);
   }
-  FRM_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = ring_quiesce(ctx);  // a frame outside the ring: the ring's frames first
+  int rc = frame_prologue(ctx, stats);
   if (rc) return rc;
-  ctx->last_is_ring = false;
-  if (stats && (rc = synchronize_all(ctx))) return rc;  // the counters must hold this frame alone
   ctx->params = params[count - 1];
   compute_scene_uniforms(ctx->params, ctx->flags, &ctx->scene);
   ctx->has_params = true;
@@ -1003,7 +712,7 @@ int frm_render_shutter(frm_ctx* ctx, uint32_t count, const frm_parameters* param
   const size_t sub_bytes = (size_t)ctx->width * ctx->height * 4u, npix_out = (size_t)ctx->out_width * ctx->out_height;
   const bool carried = chunk < count;  // several chunks: their sums go through the slot's accumulator
   if ((rc = ensure_shutter(ctx, *sl, chunk * sub_bytes, carried ? npix_out * sizeof(float4) : 0))) return rc;
-  sl->adaptive[sl->fb_idx] = sl->dof[sl->fb_idx] = false;
+  sl->no_second();
   uint8_t* frame = sl->fb();  // what shown() reads of the slot
   if (S > 1u) {
     if ((rc = ensure_res(ctx, *sl, npix_out * 4u))) return rc;
@@ -1014,91 +723,28 @@ int frm_render_shutter(frm_ctx* ctx, uint32_t count, const frm_parameters* param
   if (stats && (rc = stats_begin(ctx, s))) return rc;
   for (uint32_t first = 0; first < count; first += chunk) {
     const uint32_t n = count - first < chunk ? count - first : chunk;
-    const frm_parameters* ps = params + first;
-    SceneUniforms s0;
-    float powers[FRM_MAX_BATCH];
-    bool anim = false;
-    const bool same = batch_uniforms(ctx, n, ps, &s0, powers, &anim) == 0;
-    KernelArgs a = make_args(ctx, ps[0], s0, sl->shutter_src.p, ctx->counters, ctx->height, 0, 1, ctx->height);
-    // every launch of the frame runs on its slot (launch() takes the context's next one and moves on)
-    if (same && batch_shares_launch(ctx, a, n, anim)) {
-      set_batch(ctx, a, n, ps, powers, anim, sub_bytes);
-      ctx->next_slot = si;
-      if ((rc = launch(ctx, a, s))) return rc;
-    } else {
-      for (uint32_t k = 0; k < n; ++k) {
-        SceneUniforms sk;
-        compute_scene_uniforms(ps[k], ctx->flags, &sk);
-        a = make_args(ctx, ps[k], sk, sl->shutter_src.p + k * sub_bytes, ctx->counters, ctx->height, 0, 1, ctx->height);
-        ctx->next_slot = si;
-        if ((rc = launch(ctx, a, s))) return rc;
-      }
-    }
+    BatchUniforms u;
+    batch_uniforms(ctx, n, params + first, &u);
+    if ((rc = launch_frames(ctx, n, params + first, u, true, sl->shutter_src.p, sub_bytes,
+                            BandGeometry{ctx->height, 0, 1, ctx->height}, ctx->counters, s, (int)si)))
+      return rc;
     const bool last = first + n == count;
     FRM_HIP(ctx, launch_shutter(sl->shutter_src.p, sub_bytes, n, acc, last ? frame : nullptr, ctx->out_width,
                                 ctx->out_height, S, count * S * S, s));
   }
   FRM_HIP(ctx, hipEventRecord(sl->done, s));  // covers the accumulation
   show_slot(ctx, *sl);
-  ctx->shutter_seq = ctx->render_seq;
+  ctx->composed_seq = ctx->render_seq;
+  ctx->composed_of = "frm_render_shutter sub-frames";
   keep_render_params(ctx);
-  if (stats) {
-    uint64_t host[FRM_NUM_COUNTERS];
-    float ms = 0.0f;
-    if ((rc = stats_end(ctx, s, host, &ms)) || (rc = frm_stats_from_counters(ctx, host, stats))) return rc;
-    stats->kernel_ms = ms;
-  }
-  return FRM_OK;
+  return finish_stats(ctx, s, stats);
 }
 
-int frm_accumulate(frm_ctx* ctx, const uint8_t* dev_src, size_t src_bytes, size_t frame_stride_bytes, uint32_t count,
-                   uint32_t out_width, uint32_t out_height, uint32_t factor, float* dev_acc, size_t acc_bytes,
-                   uint32_t divisor, uint8_t* dev_dst, size_t dst_bytes, void* stream) {
-  if (!ctx || !dev_src || (!dev_acc && !dev_dst))
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "ctx/dev_src is NULL, or both dev_acc and dev_dst are");
-  if (factor == 0 || factor > FRM_MAX_SUPERSAMPLE || count == 0 || count > FRM_MAX_SHUTTER_SAMPLES)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "factor %u outside [1, %u] or count %u outside [1, %u]", factor,
-                FRM_MAX_SUPERSAMPLE, count, FRM_MAX_SHUTTER_SAMPLES);
-  const uint32_t limit = FRM_MAX_DIMENSION / factor;
-  if (out_width == 0 || out_height == 0 || out_width > limit || out_height > limit)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "output size %ux%u outside [1, %u]^2 (factor %u)", out_width, out_height,
-                limit, factor);
-  if (dev_dst && divisor == 0) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "divisor is 0");
-  const size_t npix = (size_t)out_width * out_height, frame_need = npix * factor * factor * 4u;
-  const uintptr_t sa = reinterpret_cast<uintptr_t>(dev_src), aa = reinterpret_cast<uintptr_t>(dev_acc),
-                  da = reinterpret_cast<uintptr_t>(dev_dst);
-  if (sa % 4u || da % 4u || aa % 16u)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "dev_src / dev_dst not 4-byte aligned or dev_acc not 16-byte aligned");
-  if (frame_stride_bytes % 4u || frame_stride_bytes < frame_need)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "frame stride %zu: below a frame's %zu bytes or not a multiple of 4",
-                frame_stride_bytes, frame_need);
-  if (src_bytes < frame_need || (src_bytes - frame_need) / frame_stride_bytes < count - 1u)
-    return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "src holds %zu bytes, %u frames %zu bytes apart need %zu", src_bytes, count,
-                frame_stride_bytes, (size_t)(count - 1u) * frame_stride_bytes + frame_need);
-  const size_t src_need = (size_t)(count - 1u) * frame_stride_bytes + frame_need;
-  const size_t acc_need = dev_acc ? npix * sizeof(float4) : 0, dst_need = dev_dst ? npix * 4u : 0;
-  if (acc_bytes < acc_need)
-    return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "acc holds %zu bytes, the sums need %zu", acc_bytes, acc_need);
-  if (dst_bytes < dst_need)
-    return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "dst holds %zu bytes, the frame needs %zu", dst_bytes, dst_need);
-  auto overlap = [](uintptr_t a, size_t an, uintptr_t b, size_t bn) { return an && bn && a < b + bn && b < a + an; };
-  if (overlap(sa, src_need, aa, acc_need) || overlap(sa, src_need, da, dst_need) || overlap(aa, acc_need, da, dst_need))
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "dev_src, dev_acc and dev_dst overlap");
-  FRM_HIP(ctx, hipSetDevice(ctx->device));
-  if (int rc = ring_leave(ctx)) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  FRM_HIP(ctx, launch_shutter(dev_src, frame_stride_bytes, count, dev_acc, dev_dst, out_width, out_height, factor, divisor, s));
-  return FRM_OK;
-}
-
-// frm_render of a panorama context: frm_render_shutter's steps with the six faces as the batch and
-// the projection in the place of the accumulation.
+// frm_render of a panorama context: the six faces rendered as one batch into the slot's scratch, then
+// projected into its framebuffer.
 static int render_panorama(frm_ctx* ctx, frm_stats* stats) {
-  FRM_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = ring_quiesce(ctx);  // a frame outside the ring: the ring's frames first
+  int rc = frame_prologue(ctx, stats);
   if (rc) return rc;
-  ctx->last_is_ring = false;
-  if (stats && (rc = synchronize_all(ctx))) return rc;  // the counters must hold this frame alone
   frm_parameters faces[6];
   frm_panorama_parameters(&ctx->params, ctx->panorama, faces);
   const uint32_t si = ctx->next_slot;
@@ -1110,48 +756,29 @@ static int render_panorama(frm_ctx* ctx, frm_stats* stats) {
   if ((rc = ensure_fb(ctx, *sl, (size_t)ctx->out_width * ctx->out_height * 4u)) ||
       (rc = ensure_panorama(ctx, *sl, 6u * face_bytes, ctx->out_width, ctx->out_height)))
     return rc;
-  sl->adaptive[sl->fb_idx] = sl->dof[sl->fb_idx] = false;
+  sl->no_second();
   if (stats && (rc = stats_begin(ctx, s))) return rc;
-  // the faces differ in their cameras alone (frm_panorama_parameters)
-  SceneUniforms s0;
-  float powers[FRM_MAX_BATCH];
-  bool anim = false;
-  (void)batch_uniforms(ctx, 6, faces, &s0, powers, &anim);
-  KernelArgs a = make_args(ctx, faces[0], s0, sl->pano_src.p, ctx->counters, ctx->height, 0, 1, ctx->height);
-  // every launch of the frame runs on its slot (launch() takes the context's next one and moves on)
-  if (batch_shares_launch(ctx, a, 6, anim)) {
-    set_batch(ctx, a, 6, faces, powers, anim, face_bytes);
-    ctx->next_slot = si;
-    if ((rc = launch(ctx, a, s))) return rc;
-  } else {
-    for (uint32_t k = 0; k < 6u; ++k) {
-      a = make_args(ctx, faces[k], s0, sl->pano_src.p + k * face_bytes, ctx->counters, ctx->height, 0, 1, ctx->height);
-      ctx->next_slot = si;
-      if ((rc = launch(ctx, a, s))) return rc;
-    }
-  }
+  // the faces differ in their cameras alone (frm_panorama_parameters): frame 0's scene uniforms serve all
+  BatchUniforms u;
+  batch_uniforms(ctx, 6, faces, &u);
+  if ((rc = launch_frames(ctx, 6, faces, u, false, sl->pano_src.p, face_bytes,
+                          BandGeometry{ctx->height, 0, 1, ctx->height}, ctx->counters, s, (int)si)))
+    return rc;
   FRM_HIP(ctx, launch_project_equirect(sl->pano_src.p, face_bytes, ctx->panorama, (const float*)sl->pano_tables.p,
                                        sl->fb(), ctx->out_width, ctx->out_height, s));
   FRM_HIP(ctx, hipEventRecord(sl->done, s));  // covers the projection
   show_slot(ctx, *sl);
-  ctx->panorama_seq = ctx->render_seq;
+  ctx->composed_seq = ctx->render_seq;
+  ctx->composed_of = "a panorama's faces (frm_set_panorama)";
   keep_render_params(ctx);
-  if (stats) {
-    uint64_t host[FRM_NUM_COUNTERS];
-    float ms = 0.0f;
-    if ((rc = stats_end(ctx, s, host, &ms)) || (rc = frm_stats_from_counters(ctx, host, stats))) return rc;
-    stats->kernel_ms = ms;
-  }
-  return FRM_OK;
+  return finish_stats(ctx, s, stats);
 }
 
 int frm_set_panorama(frm_ctx* ctx, uint32_t face_size) {
   if (!ctx) return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "ctx is NULL");
   if (face_size) {
     if (ctx->group) return not_on_group(ctx, "frm_set_panorama");
-    if (ctx->supersample > 1u) return not_supersampled(ctx, "frm_set_panorama");
-    if (ctx->adaptive > 1u) return not_adaptive(ctx, "frm_set_panorama");
-    if (ctx->dof_radius) return not_dof(ctx, "frm_set_panorama");
+    if (other_mode(ctx, kPanorama)) return refuse_mode(ctx, "frm_set_panorama");
     // the six faces are one batch in one scratch: 1 GiB of it at most, and a shared launch's u32
     // fetch positions (frm_render_bands_batch)
     const uint64_t m = (uint64_t)face_size + 2u, npix = 6u * m * m;
@@ -1183,109 +810,12 @@ int frm_get_panorama(const frm_ctx* ctx, uint32_t* out_face_size) {
   return FRM_OK;
 }
 
-int frm_panorama_face_size(uint32_t width, uint32_t* out_face_size) {
-  if (!out_face_size || width == 0 || width > FRM_MAX_DIMENSION)
-    return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "out_face_size is NULL or width %u outside [1, %u]", width,
-                FRM_MAX_DIMENSION);
-  *out_face_size = (width + 3u) / 4u;
-  return FRM_OK;
-}
-
-int frm_equirect_tables(uint32_t width, uint32_t height, float* sin_lon, float* cos_lon, float* sin_lat,
-                        float* cos_lat) {
-  if (!sin_lon || !cos_lon || !sin_lat || !cos_lat || width == 0 || height == 0 || width > FRM_MAX_DIMENSION ||
-      height > FRM_MAX_DIMENSION)
-    return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "a table is NULL or size %ux%u outside [1, %u]^2", width, height,
-                FRM_MAX_DIMENSION);
-  float* t = new (std::nothrow) float[2u * (size_t)width + 2u * (size_t)height];
-  if (!t) return fail(nullptr, FRM_ERR_OUT_OF_MEMORY, "host allocation failed");
-  equirect_tables(width, height, t);
-  memcpy(sin_lon, t, width * sizeof(float));
-  memcpy(cos_lon, t + width, width * sizeof(float));
-  memcpy(sin_lat, t + 2u * (size_t)width, height * sizeof(float));
-  memcpy(cos_lat, t + 2u * (size_t)width + height, height * sizeof(float));
-  delete[] t;
-  return FRM_OK;
-}
-
-int frm_project_equirect(frm_ctx* ctx, const uint8_t* dev_faces, size_t faces_bytes, size_t face_stride_bytes,
-                         uint32_t face_size, uint8_t* dev_dst, size_t dst_bytes, uint32_t out_width,
-                         uint32_t out_height, void* stream) {
-  if (!ctx || !dev_faces || !dev_dst) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "ctx/dev_faces/dev_dst is NULL");
-  if (face_size == 0 || face_size > FRM_MAX_DIMENSION - 2u)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "face size %u outside [1, %u]", face_size, FRM_MAX_DIMENSION - 2u);
-  if (out_width == 0 || out_height == 0 || out_width > FRM_MAX_DIMENSION || out_height > FRM_MAX_DIMENSION)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "output size %ux%u outside [1, %u]^2", out_width, out_height,
-                FRM_MAX_DIMENSION);
-  const size_t m = (size_t)face_size + 2u, face_need = m * m * 4u;
-  const uintptr_t fa = reinterpret_cast<uintptr_t>(dev_faces), da = reinterpret_cast<uintptr_t>(dev_dst);
-  if (fa % 4u || da % 4u) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "dev_faces / dev_dst not 4-byte aligned");
-  if (face_stride_bytes % 4u || face_stride_bytes < face_need)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "face stride %zu: below a face's %zu bytes or not a multiple of 4",
-                face_stride_bytes, face_need);
-  if (faces_bytes < face_need || (faces_bytes - face_need) / face_stride_bytes < 5u)
-    return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "faces hold %zu bytes, six faces %zu bytes apart need %zu", faces_bytes,
-                face_stride_bytes, 5u * face_stride_bytes + face_need);
-  const size_t src_need = 5u * face_stride_bytes + face_need, dst_need = (size_t)out_width * out_height * 4u;
-  if (dst_bytes < dst_need)
-    return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "dst holds %zu bytes, the panorama needs %zu", dst_bytes, dst_need);
-  if (fa < da + dst_need && da < fa + src_need)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "dev_faces and dev_dst overlap");
-  FRM_HIP(ctx, hipSetDevice(ctx->device));
-  if (int rc = ring_leave(ctx)) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  // the tables are scratch per call, allocated and released in the order of the call's stream: calls
-  // in flight on different streams never share them
-  float* tables = nullptr;
-  int rc = dev_alloc(ctx, (void**)&tables, (2u * (size_t)out_width + 2u * (size_t)out_height) * sizeof(float), s);
-  if (rc) return rc;
-  hipError_t e = hipSuccess;
-  if (!(rc = upload_tables(ctx, tables, out_width, out_height, s)))
-    e = launch_project_equirect(dev_faces, face_stride_bytes, face_size, tables, dev_dst, out_width, out_height, s);
-  const int r1 = dev_release(ctx, tables, s);
-  if (rc) return rc;
-  if (e != hipSuccess) return hip_fail(ctx, e, "launch_project_equirect");
-  return r1;
-}
-
-int frm_dof_coc(float aperture, float focus, uint32_t max_radius, const float* depth, size_t n, float* out_c) {
-  if (!depth || !out_c) return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "depth/out_c is NULL");
-  if (int rc = check_lens(nullptr, aperture, focus, max_radius)) return rc;
-  dof_coc_host(aperture, focus, max_radius, depth, n, out_c);
-  return FRM_OK;
-}
-
-int frm_depth_of_field(frm_ctx* ctx, const uint8_t* dev_src, size_t src_bytes, const float* dev_depth,
-                       size_t depth_bytes, uint32_t width, uint32_t height, float aperture, float focus,
-                       uint32_t max_radius, uint8_t* dev_dst, size_t dst_bytes, void* stream) {
-  if (!ctx || !dev_src || !dev_depth || !dev_dst)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "ctx/dev_src/dev_depth/dev_dst is NULL");
-  if (width == 0 || height == 0 || width > FRM_MAX_DIMENSION || height > FRM_MAX_DIMENSION)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "frame size %ux%u outside [1, %u]^2", width, height, FRM_MAX_DIMENSION);
-  if (int rc = check_lens(ctx, aperture, focus, max_radius)) return rc;
-  const size_t need = (size_t)width * height * 4u;  // of each of the three
-  if (int rc = check_src_dst(ctx, dev_src, src_bytes, width, height, dev_dst, dst_bytes, need, "frame")) return rc;
-  const uintptr_t za = reinterpret_cast<uintptr_t>(dev_depth), da = reinterpret_cast<uintptr_t>(dev_dst);
-  if (za % 4u) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "dev_depth not 4-byte aligned");
-  if (depth_bytes < need)
-    return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "depth holds %zu bytes, %ux%u floats need %zu", depth_bytes, width, height,
-                need);
-  if (za < da + need && da < za + need) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "dev_depth and dev_dst overlap");
-  FRM_HIP(ctx, hipSetDevice(ctx->device));
-  if (int rc = ring_leave(ctx)) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  FRM_HIP(ctx, launch_dof(dev_src, dev_depth, dev_dst, width, height, aperture, focus, max_radius, s));
-  return FRM_OK;
-}
-
 int frm_set_depth_of_field(frm_ctx* ctx, float aperture, float focus, uint32_t max_radius) {
   if (!ctx) return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "ctx is NULL");
   if (max_radius) {
     if (int rc = check_lens(ctx, aperture, focus, max_radius)) return rc;
     if (ctx->group) return not_on_group(ctx, "frm_set_depth_of_field");
-    if (ctx->supersample > 1u) return not_supersampled(ctx, "frm_set_depth_of_field");
-    if (ctx->adaptive > 1u) return not_adaptive(ctx, "frm_set_depth_of_field");
-    if (ctx->panorama) return not_panorama(ctx, "frm_set_depth_of_field");
+    if (other_mode(ctx, kDof)) return refuse_mode(ctx, "frm_set_depth_of_field");
     if (ctx->flags & FRM_FLAG_SIMPLE_KERNEL)
       return fail(ctx, FRM_ERR_UNSUPPORTED,
                   "frm_set_depth_of_field: the depth plane comes from the persistent kernel's records; not available "
@@ -1321,221 +851,6 @@ int frm_get_depth_of_field(const frm_ctx* ctx, float* out_aperture, float* out_f
   *out_aperture = ctx->dof_aperture;
   *out_focus = ctx->dof_focus;
   *out_max_radius = ctx->dof_radius;
-  return FRM_OK;
-}
-
-int frm_unshuffle_bands(frm_ctx* ctx, const uint8_t* dev_src, size_t rank_stride_bytes, uint8_t* dev_dst,
-                        size_t dst_bytes, uint32_t band_rows, uint32_t ranks, void* stream) {
-  if (!ctx || !dev_src || !dev_dst || band_rows == 0 || ranks == 0)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "invalid unshuffle arguments");
-  if (ctx->supersample > 1u) return not_supersampled(ctx, "frm_unshuffle_bands");
-  if (ctx->adaptive > 1u) return not_adaptive(ctx, "frm_unshuffle_bands");
-  if (ctx->panorama) return not_panorama(ctx, "frm_unshuffle_bands");
-  if (ctx->dof_radius) return not_dof(ctx, "frm_unshuffle_bands");
-  if (!ctx->width) return fail(ctx, FRM_ERR_NOT_READY, "frm_resize has not been called");
-  size_t need = (size_t)ctx->width * ctx->height * 4u;
-  if (dst_bytes < need)
-    return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "dst holds %zu bytes, frame needs %zu", dst_bytes, need);
-  uint32_t rows = band_local_rows(ctx->height, band_rows, 0, ranks);
-  if (rank_stride_bytes < (size_t)rows * ctx->width * 4u)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "rank stride %zu below one rank's bands", rank_stride_bytes);
-  if (rank_stride_bytes % 4u)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "rank stride must be a multiple of 4");
-  FRM_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  FRM_HIP(ctx, launch_unshuffle(dev_src, rank_stride_bytes, dev_dst, ctx->width, ctx->height, band_rows,
-                                ranks, s));
-  return FRM_OK;
-}
-
-#ifdef FRM_STAMPS
-extern "C" int frm_debug_read(frm_ctx* ctx, uint64_t* out5) {
-  const Slot& sl = ctx->slots[(ctx->next_slot + ctx->nslots - 1u) % ctx->nslots];  // last launch
-  return hipMemcpy(out5, sl.queue + kQueueDebugWord, 40, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 1;
-}
-#endif
-
-// The scheduling state in the slot of the last persistent launch, copied out for
-// frm_debug_pixel_keys (keys) and frm_debug_pixel_order (order, ranked): min(n, that launch's
-// local pixels) entries, the count in *copied. Returns a frm_status.
-static int debug_sched_read(frm_ctx* ctx, const char* what, uint8_t* keys, uint32_t* order, uint32_t* ranked, size_t n,
-                            size_t* copied) {
-  if (ctx->group) return not_on_group(ctx, what);
-  if (int rc = ring_leave(ctx)) return rc;
-  const Slot& sl = ctx->slots[(ctx->next_slot + ctx->nslots - 1u) % ctx->nslots];  // last launch
-  if (!sl.sched_keys || !sl.sched_order || !sl.sched_npix)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "%s: no persistent launch yet", what);
-  if (n > sl.sched_npix) n = sl.sched_npix;
-  FRM_HIP(ctx, hipSetDevice(ctx->device));
-  FRM_HIP(ctx, hipDeviceSynchronize());
-  if (keys) FRM_HIP(ctx, hipMemcpy(keys, sl.sched_keys, n, hipMemcpyDeviceToHost));
-  if (order) FRM_HIP(ctx, hipMemcpy(order, sl.sched_order, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (ranked) *ranked = sl.order_ready ? 1u : 0u;
-  *copied = n;
-  return FRM_OK;
-}
-
-// per-pixel cost keys recorded by the last persistent launch (local pixel order; before
-// the next launch overwrites them); the count copied, or a negative frm_status
-int frm_debug_pixel_keys(frm_ctx* ctx, uint8_t* out, size_t n) {
-  if (!ctx || !out) return -fail(ctx, FRM_ERR_INVALID_ARGUMENT, "NULL argument");
-  size_t copied = 0;
-  const int rc = debug_sched_read(ctx, "frm_debug_pixel_keys", out, nullptr, nullptr, n, &copied);
-  return rc ? -rc : (int)copied;
-}
-
-// the fetch order in the last persistent launch's slot: the one that launch ranked for the slot's
-// next launch of the same geometry (*out_ranked = 1), else the one it fetched by itself (0)
-int frm_debug_pixel_order(frm_ctx* ctx, uint32_t* out, size_t n, uint32_t* out_ranked) {
-  if (!ctx || !out || !out_ranked) return -fail(ctx, FRM_ERR_INVALID_ARGUMENT, "NULL argument");
-  size_t copied = 0;
-  const int rc = debug_sched_read(ctx, "frm_debug_pixel_order", nullptr, out, out_ranked, n, &copied);
-  return rc ? -rc : (int)copied;
-}
-
-// replaces the cost keys the next launch sorts its pixels by (scheduling experiments): the
-// slot of the next launch must hold the history of a whole frame of the current size
-int frm_debug_set_pixel_keys(frm_ctx* ctx, const uint8_t* keys, size_t n) {
-  if (!ctx || !keys) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (ctx->group) return not_on_group(ctx, "frm_debug_set_pixel_keys");
-  if (int rc = ring_leave(ctx)) return rc;
-  Slot& sl = ctx->slots[ctx->next_slot];
-  if (!sl.sched_history || !sl.sched_whole || sl.sched_w != ctx->width || sl.sched_h != ctx->height ||
-      n != (size_t)ctx->width * ctx->height || n > sl.sched_cap)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "no whole-frame history of this size in the next slot");
-  FRM_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = wait_slot(ctx, sl);
-  if (rc) return rc;
-  if (sl.keys_reader) FRM_HIP(ctx, hipEventSynchronize(sl.keys_read));
-  FRM_HIP(ctx, hipMemcpy(sl.sched_keys, keys, n, hipMemcpyHostToDevice));
-  sl.order_ready = false;  // the next launch sorts by these keys
-  return FRM_OK;
-}
-
-// per-pixel shading inputs of the last frm_render (a whole persistent frame of the current size
-// and parameters): 10 floats per pixel, row-major, as the oracle's om_render_trace
-int frm_debug_trace(frm_ctx* ctx, float* out, size_t n_floats) {
-  int rc = ensure_ready(ctx);
-  if (rc) return rc;
-  if (ctx->group) return not_on_group(ctx, "frm_debug_trace");
-  if ((rc = ring_leave(ctx))) return rc;
-  if (!out) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "out is NULL");
-  const size_t npix = (size_t)ctx->width * ctx->height;
-  if (n_floats < npix * 10u)
-    return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "out holds %zu floats, the trace needs %zu", n_floats, npix * 10u);
-  const Slot& sl = ctx->slots[ctx->last_slot];
-  if (ctx->render_seq && ctx->shutter_seq == ctx->render_seq && !ctx->last_is_ring)
-    return fail(ctx, FRM_ERR_NOT_READY, "the last frame was a frm_render_shutter frame: no single frame to trace");
-  if (ctx->render_seq && ctx->panorama_seq == ctx->render_seq && !ctx->last_is_ring)
-    return fail(ctx, FRM_ERR_NOT_READY, "the last frame was a panorama (frm_set_panorama): no single frame to trace");
-  if (!ctx->render_seq || sl.seq != ctx->render_seq)
-    return fail(ctx, FRM_ERR_NOT_READY, "no frm_render, or a later launch reused its slot's records");
-  if (!sl.records.p || sl.records.cap < npix * kRecordBytes || !sl.sched_whole || sl.sched_w != ctx->width || sl.sched_h != ctx->height)
-    return fail(ctx, FRM_ERR_NOT_READY, "the last frm_render was not a persistent launch of this frame size");
-  FRM_HIP(ctx, hipSetDevice(ctx->device));
-  // the rays and colours of that render: its own parameters, not those set since
-  KernelArgs a = make_args(ctx, ctx->render_params, ctx->render_scene, sl.fb(), ctx->counters, ctx->height, 0, 1,
-                           ctx->height);
-  a.geom = reinterpret_cast<ShadeGeom*>(sl.records.p);
-  a.tails = record_tails(sl.records);
-  float* d = nullptr;
-  FRM_HIP(ctx, hipMalloc(&d, npix * 10u * sizeof(float)));
-  hipError_t e = launch_trace(a, d, sl.stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d, npix * 10u * sizeof(float), hipMemcpyDeviceToHost, sl.stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(sl.stream);
-  (void)hipFree(d);
-  if (e != hipSuccess) return hip_fail(ctx, e, "frm_debug_trace");
-  return FRM_OK;
-}
-
-// the depth plane of the last frm_render (frm_debug_trace's conditions): the plane its gather used
-// on a depth-of-field context, else depth_pass over the records now
-int frm_read_depth(frm_ctx* ctx, float* dst, size_t n_floats) {
-  int rc = ensure_ready(ctx);
-  if (rc) return rc;
-  if (ctx->group) return not_on_group(ctx, "frm_read_depth");
-  if ((rc = ring_leave(ctx))) return rc;
-  if (!dst) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "dst is NULL");
-  const size_t npix = (size_t)ctx->width * ctx->height;
-  if (n_floats < npix)
-    return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "dst holds %zu floats, the depth plane needs %zu", n_floats, npix);
-  const Slot& sl = ctx->slots[ctx->last_slot];
-  if (ctx->render_seq && ctx->shutter_seq == ctx->render_seq && !ctx->last_is_ring)
-    return fail(ctx, FRM_ERR_NOT_READY, "the last frame was a frm_render_shutter frame: no single frame's depth");
-  if (ctx->render_seq && ctx->panorama_seq == ctx->render_seq && !ctx->last_is_ring)
-    return fail(ctx, FRM_ERR_NOT_READY, "the last frame was a panorama (frm_set_panorama): no single frame's depth");
-  if (!ctx->render_seq || sl.seq != ctx->render_seq)
-    return fail(ctx, FRM_ERR_NOT_READY, "no frm_render, or a later launch reused its slot's records");
-  if (!sl.records.p || sl.records.cap < npix * kRecordBytes || !sl.sched_whole || sl.sched_w != ctx->width || sl.sched_h != ctx->height)
-    return fail(ctx, FRM_ERR_NOT_READY, "the last frm_render was not a persistent launch of this frame size");
-  FRM_HIP(ctx, hipSetDevice(ctx->device));
-  hipError_t e = hipSuccess;
-  if (sl.dof[sl.fb_idx] && sl.depth.p && sl.depth_w == ctx->width && sl.depth_h == ctx->height) {
-    e = hipMemcpyAsync(dst, sl.depth.p, npix * sizeof(float), hipMemcpyDeviceToHost, sl.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(sl.stream);
-  } else {
-    // the plane is scratch of the call, from the context's pool in the order of the slot's stream: no
-    // device-wide synchronisation, frames in flight on other slots go on
-    float* d = nullptr;
-    if ((rc = dev_alloc(ctx, (void**)&d, npix * sizeof(float), sl.stream))) return rc;
-    e = launch_depth(reinterpret_cast<const ShadeGeom*>(sl.records.p), record_tails(sl.records), d, (uint32_t)npix, sl.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dst, d, npix * sizeof(float), hipMemcpyDeviceToHost, sl.stream);
-    const int r1 = dev_release(ctx, d, sl.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(sl.stream);
-    if (e == hipSuccess && r1) return r1;
-  }
-  if (e != hipSuccess) return hip_fail(ctx, e, "frm_read_depth");
-  return FRM_OK;
-}
-
-int frm_stats_from_counters(const frm_ctx* ctx, const uint64_t* c, frm_stats* out) {
-  if (!ctx || !c || !out) return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "NULL argument");
-  memset(out, 0, sizeof(*out));
-  out->pixels = c[kCntPixels];
-  out->hit_pixels = c[kCntHits];
-  out->primary_steps = c[kCntPrimary];
-  out->shadow_steps = c[kCntShadow];
-  out->normal_evals = c[kCntNormal];
-  out->fractal_bodies = c[kCntBodies];
-  out->fractal_bailouts = c[kCntBailouts];
-  out->march_steps = c[kCntPrimary] + c[kCntShadow];
-  out->wom_ops = wom_ops(ctx->scene, c);
-  return FRM_OK;
-}
-
-int frm_eval_scene(frm_ctx* ctx, const float* points, uint32_t n, float* out_distance, float* out_color) {
-  if (!ctx || !points || !out_distance || !out_color)
-    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (!ctx->has_params) return fail(ctx, FRM_ERR_NOT_READY, "frm_set_parameters has not been called");
-  if (n == 0) return FRM_OK;
-  FRM_HIP(ctx, hipSetDevice(ctx->device));
-  float* d = nullptr;
-  FRM_HIP(ctx, hipMalloc(&d, (size_t)n * 7 * sizeof(float)));
-  float *pts = d, *dist = d + 3 * (size_t)n, *col = d + 4 * (size_t)n;
-  hipError_t e = hipMemcpyAsync(pts, points, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = launch_eval_scene(ctx->scene, pts, n, dist, col, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out_distance, dist, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out_color, col, (size_t)n * 12, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d);
-  if (e != hipSuccess) return hip_fail(ctx, e, "frm_eval_scene");
-  return FRM_OK;
-}
-
-int frm_eval_math(frm_ctx* ctx, int32_t fn, const float* a, const float* b, uint32_t n, float* out) {
-  if (!ctx || !a || !out || fn < 0 || fn > FRM_MATH_LAST) return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "bad argument");
-  if (n == 0) return FRM_OK;
-  FRM_HIP(ctx, hipSetDevice(ctx->device));
-  float* d = nullptr;
-  FRM_HIP(ctx, hipMalloc(&d, (size_t)n * 3 * sizeof(float)));
-  float *da = d, *db = b ? d + n : nullptr, *dout = d + 2 * (size_t)n;
-  hipError_t e = hipMemcpyAsync(da, a, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && b) e = hipMemcpyAsync(db, b, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = launch_eval_math(fn, da, db, n, dout, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d);
-  if (e != hipSuccess) return hip_fail(ctx, e, "frm_eval_math");
   return FRM_OK;
 }
 

@@ -71,6 +71,27 @@ static int check(int rc, frm_ctx* ctx, const char* what) {
   return rc;
 }
 
+// An option's integer in [lo, hi], or its float in (0, hi] (positive) or [0, hi]; anything else ends
+// the run with the option's complaint.
+static uint32_t parse_uint(const char* opt, const char* v, long lo, long hi) {
+  char* end = nullptr;
+  const long k = strtol(v, &end, 10);
+  if (end == v || *end || k < lo || k > hi) {
+    fprintf(stderr, "frm_render: %s %s outside [%ld, %ld]\n", opt, v, lo, hi);
+    exit(2);
+  }
+  return (uint32_t)k;
+}
+static float parse_float(const char* opt, const char* v, bool positive, float hi, const char* complaint) {
+  char* end = nullptr;
+  const float x = strtof(v, &end);
+  if (end == v || *end || !(positive ? x > 0.0f : x >= 0.0f) || x > hi) {
+    fprintf(stderr, "frm_render: %s %s%s\n", opt, v, complaint);
+    exit(2);
+  }
+  return x;
+}
+
 static int write_ppm(const char* out, uint32_t fr, const uint8_t* rgba, uint32_t width, uint32_t height,
                      char* name, size_t name_len) {
   if (strchr(out, '%')) snprintf(name, name_len, out, fr);
@@ -208,126 +229,58 @@ int main(int argc, char** argv) {
     else if (!strcmp(a, "--time-factor")) time_factor = (float)atof(next());
     else if (!strcmp(a, "--gpus")) gpus = (uint32_t)atoi(next());
     else if (!strcmp(a, "--batch")) batch = (uint32_t)atoi(next());
-    else if (!strcmp(a, "--ssaa")) {
-      const char* v = next();
-      char* end = nullptr;
-      const long k = strtol(v, &end, 10);
-      if (end == v || *end || k < 1 || k > (long)FRM_MAX_SUPERSAMPLE) {
-        fprintf(stderr, "frm_render: --ssaa %s outside [1, %u]\n", v, FRM_MAX_SUPERSAMPLE);
-        return 2;
-      }
-      ssaa = (uint32_t)k;
-      ssaa_given = true;
-    }
-    else if (!strcmp(a, "--adaptive") || !strcmp(a, "--edge-threshold")) {
-      const bool thr = a[2] == 'e';
-      const long hi = thr ? 256 : (long)FRM_MAX_SUPERSAMPLE, lo = thr ? 0 : 1;
-      const char* v = next();
-      char* end = nullptr;
-      const long k = strtol(v, &end, 10);
-      if (end == v || *end || k < lo || k > hi) {
-        fprintf(stderr, "frm_render: %s %s outside [%ld, %ld]\n", a, v, lo, hi);
-        return 2;
-      }
-      (thr ? edge_threshold : adaptive) = (uint32_t)k;
-      adaptive_given = true;
-    }
-    else if (!strcmp(a, "--shutter-samples")) {
-      const char* v = next();
-      char* end = nullptr;
-      const long k = strtol(v, &end, 10);
-      if (end == v || *end || k < 1 || k > (long)FRM_MAX_SHUTTER_SAMPLES) {
-        fprintf(stderr, "frm_render: --shutter-samples %s outside [1, %u]\n", v, FRM_MAX_SHUTTER_SAMPLES);
-        return 2;
-      }
-      shutter_samples = (uint32_t)k;
-    }
-    else if (!strcmp(a, "--shutter")) {
-      const char* v = next();
-      char* end = nullptr;
-      shutter = strtof(v, &end);
-      if (end == v || *end || !(shutter > 0.0f && shutter <= 1.0f)) {
-        fprintf(stderr, "frm_render: --shutter %s outside (0, 1]\n", v);
-        return 2;
-      }
-    }
+    else if (!strcmp(a, "--ssaa")) { ssaa = parse_uint(a, next(), 1, FRM_MAX_SUPERSAMPLE); ssaa_given = true; }
+    else if (!strcmp(a, "--adaptive")) { adaptive = parse_uint(a, next(), 1, FRM_MAX_SUPERSAMPLE); adaptive_given = true; }
+    else if (!strcmp(a, "--edge-threshold")) { edge_threshold = parse_uint(a, next(), 0, 256); adaptive_given = true; }
+    else if (!strcmp(a, "--shutter-samples")) shutter_samples = parse_uint(a, next(), 1, FRM_MAX_SHUTTER_SAMPLES);
+    else if (!strcmp(a, "--shutter")) shutter = parse_float(a, next(), true, 1.0f, " outside (0, 1]");
     else if (!strcmp(a, "--panorama")) panorama = true;
-    else if (!strcmp(a, "--face-size")) {
-      const char* v = next();
-      char* end = nullptr;
-      const long k = strtol(v, &end, 10);
-      if (end == v || *end || k < 1 || k > (long)FRM_MAX_DIMENSION - 2) {
-        fprintf(stderr, "frm_render: --face-size %s outside [1, %u]\n", v, FRM_MAX_DIMENSION - 2u);
-        return 2;
-      }
-      face_size = (uint32_t)k;
+    else if (!strcmp(a, "--face-size")) face_size = parse_uint(a, next(), 1, FRM_MAX_DIMENSION - 2);
+    else if (!strcmp(a, "--dof-aperture")) {
+      dof_aperture = parse_float(a, next(), false, 3.402823466e+38f, ": not a finite non-negative number");
+      dof_aperture_given = true;
     }
-    else if (!strcmp(a, "--dof-aperture") || !strcmp(a, "--dof-focus")) {
-      const bool foc = a[6] == 'f';
-      const char* v = next();
-      char* end = nullptr;
-      const float x = strtof(v, &end);
-      if (end == v || *end || !(foc ? x > 0.0f : x >= 0.0f) || x > 3.402823466e+38f) {
-        fprintf(stderr, "frm_render: %s %s: not a finite %s number\n", a, v, foc ? "positive" : "non-negative");
-        return 2;
-      }
-      (foc ? dof_focus : dof_aperture) = x;
-      (foc ? dof_focus_given : dof_aperture_given) = true;
+    else if (!strcmp(a, "--dof-focus")) {
+      dof_focus = parse_float(a, next(), true, 3.402823466e+38f, ": not a finite positive number");
+      dof_focus_given = true;
     }
-    else if (!strcmp(a, "--dof-radius")) {
-      const char* v = next();
-      char* end = nullptr;
-      const long k = strtol(v, &end, 10);
-      if (end == v || *end || k < 1 || k > (long)FRM_MAX_DOF_RADIUS) {
-        fprintf(stderr, "frm_render: --dof-radius %s outside [1, %u]\n", v, FRM_MAX_DOF_RADIUS);
-        return 2;
-      }
-      dof_radius = (uint32_t)k;
-      dof_radius_given = true;
-    }
+    else if (!strcmp(a, "--dof-radius")) { dof_radius = parse_uint(a, next(), 1, FRM_MAX_DOF_RADIUS); dof_radius_given = true; }
     else if (!strcmp(a, "--depth-out")) depth_out = next();
     else { fprintf(stderr, "unknown argument %s\n", a); return 2; }
   }
   const bool dof = dof_aperture_given || dof_focus_given || dof_radius_given;
-  if (dof && !(dof_aperture_given && dof_focus_given)) {
-    fprintf(stderr, "frm_render: depth of field needs both --dof-aperture and --dof-focus\n");
-    return 2;
-  }
-  if (dof && (ssaa_given || adaptive_given || shutter_samples > 1 || panorama || batch > 1 || gpus > 0)) {
-    fprintf(stderr, "frm_render: --dof-* excludes --ssaa, --adaptive, --shutter-samples, --panorama, --batch and --gpus "
-                    "(the gather works on one plain frame and its depth)\n");
-    return 2;
-  }
-  if (dof && (flags & FRM_FLAG_SIMPLE_KERNEL)) {
-    fprintf(stderr, "frm_render: --dof-* excludes --simple (the depth plane comes from the persistent kernel)\n");
-    return 2;
-  }
-  if (depth_out && (batch > 1 || gpus > 0 || panorama || shutter_samples > 1)) {
-    fprintf(stderr, "frm_render: --depth-out excludes --batch, --gpus, --panorama and --shutter-samples (no single "
-                    "frame's depth)\n");
-    return 2;
-  }
-  if (face_size && !panorama) {
-    fprintf(stderr, "frm_render: --face-size needs --panorama\n");
-    return 2;
-  }
-  if (panorama && (ssaa_given || adaptive_given || shutter_samples > 1 || batch > 1 || gpus > 0)) {
-    fprintf(stderr, "frm_render: --panorama excludes --ssaa, --adaptive, --shutter-samples, --batch and --gpus (for an "
-                    "anti-aliased panorama project the faces to a larger frame with frm_project_equirect and "
-                    "frm_resolve it)\n");
-    return 2;
-  }
+  // what may not be combined: (the options given, what they exclude or lack, the complaint), the first
+  // that holds is reported
+  const bool many = batch > 1 || gpus > 0, blur = shutter_samples > 1;
+  const struct {
+    bool given, clash;
+    const char* complaint;
+  } rules[] = {
+      {dof, !(dof_aperture_given && dof_focus_given), "depth of field needs both --dof-aperture and --dof-focus"},
+      {dof, ssaa_given || adaptive_given || blur || panorama || many,
+       "--dof-* excludes --ssaa, --adaptive, --shutter-samples, --panorama, --batch and --gpus "
+       "(the gather works on one plain frame and its depth)"},
+      {dof, (flags & FRM_FLAG_SIMPLE_KERNEL) != 0,
+       "--dof-* excludes --simple (the depth plane comes from the persistent kernel)"},
+      {depth_out != nullptr, many || panorama || blur,
+       "--depth-out excludes --batch, --gpus, --panorama and --shutter-samples (no single frame's depth)"},
+      {face_size != 0, !panorama, "--face-size needs --panorama"},
+      {panorama, ssaa_given || adaptive_given || blur || many,
+       "--panorama excludes --ssaa, --adaptive, --shutter-samples, --batch and --gpus (for an "
+       "anti-aliased panorama project the faces to a larger frame with frm_project_equirect and "
+       "frm_resolve it)"},
+      {ssaa_given, adaptive_given, "--adaptive / --edge-threshold and --ssaa exclude each other"},
+      {blur, many || adaptive > 1,
+       "--shutter-samples excludes --batch, --adaptive and --gpus (frm_render_shutter batches "
+       "its sub-frames on one plain or supersampled context)"},
+  };
+  for (const auto& r : rules)
+    if (r.given && r.clash) {
+      fprintf(stderr, "frm_render: %s\n", r.complaint);
+      return 2;
+    }
   if (panorama && !face_size && frm_panorama_face_size(width, &face_size) != FRM_OK) {
     fprintf(stderr, "frm_render: --panorama: %s\n", frm_last_error(nullptr));
-    return 2;
-  }
-  if (ssaa_given && adaptive_given) {
-    fprintf(stderr, "frm_render: --adaptive / --edge-threshold and --ssaa exclude each other\n");
-    return 2;
-  }
-  if (shutter_samples > 1 && (batch > 1 || adaptive > 1 || gpus > 0)) {
-    fprintf(stderr, "frm_render: --shutter-samples excludes --batch, --adaptive and --gpus (frm_render_shutter batches "
-                    "its sub-frames on one plain or supersampled context)\n");
     return 2;
   }
   frm_ctx* ctx = nullptr;
@@ -361,6 +314,10 @@ int main(int argc, char** argv) {
   frm_timing_init(&timing);
   timing.time_factor = time_factor;
   frm_parameters_update_camera_from(&p, &cam);
+  if (batch < 1 || batch > FRM_MAX_BATCH) {
+    fprintf(stderr, "frm_render: --batch %u outside [1, %u]\n", batch, FRM_MAX_BATCH);
+    return 2;
+  }
   // --batch drives the bands itself: a plain context at the render size, resolved frame by frame
   if (batch > 1) {
     check(frm_resize(ctx, ssaa * width, ssaa * height), ctx, "frm_resize");
@@ -372,10 +329,6 @@ int main(int argc, char** argv) {
     if (dof) check(frm_set_depth_of_field(ctx, dof_aperture, dof_focus, dof_radius), ctx, "frm_set_depth_of_field");
   }
   std::vector<uint8_t> rgba((size_t)width * height * 4);
-  if (batch < 1 || batch > FRM_MAX_BATCH) {
-    fprintf(stderr, "frm_render: --batch %u outside [1, %u]\n", batch, FRM_MAX_BATCH);
-    return 2;
-  }
   if (batch > 1 && gpus > 0) {
     fprintf(stderr, "frm_render: --batch renders on one GPU (frm_render_bands_batch is a per-device entry point)\n");
     return 2;
@@ -400,13 +353,7 @@ int main(int argc, char** argv) {
     }
     check(frm_read_frame(ctx, rgba.data(), rgba.size()), ctx, "frm_read_frame");
     char name[4096];
-    if (strchr(out, '%')) snprintf(name, sizeof(name), out, fr);
-    else snprintf(name, sizeof(name), "%s", out);
-    FILE* f = fopen(name, "wb");
-    if (!f) { perror(name); return 1; }
-    fprintf(f, "P6\n%u %u\n255\n", width, height);
-    for (size_t i = 0; i < (size_t)width * height; ++i) fwrite(&rgba[4 * i], 1, 3, f);
-    fclose(f);
+    if (write_ppm(out, fr, rgba.data(), width, height, name, sizeof(name))) return 1;
     printf("{\"frame\": %u, \"out\": \"%s\", \"width\": %u, \"height\": %u, \"time\": %.6f, "
            "\"pos\": [%.5f, %.5f, %.5f], \"yaw\": %.5f, \"pitch\": %.5f, \"kernel_ms\": %.3f, "
            "\"march_steps\": %llu, \"hit_pixels\": %llu, \"gsteps_per_s\": %.3f, \"ssaa\": %u, "

@@ -1,5 +1,5 @@
 // frm_ctx.h — the context behind include/frm.h's opaque frm_ctx, and what the host layer's files
-// (frm_api.hip, frm_launch.hip, frm_group.hip, frm_ring.hip) share.
+// (frm_api.hip, frm_stages.hip, frm_debug.hip, frm_launch.hip, frm_group.hip, frm_ring.hip) share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -53,6 +53,26 @@ static constexpr uint64_t kInflightCapPixels = 4ull * 3840u * 2160u;
 // profiles/round5/dropin_bpc8); multi-frame launches interleave their frames' tails and take 8.
 static constexpr int kLoneFrameBlocksPerCu = 28;
 
+// What a context's frm_render makes of a frame. The four modes beyond kPlain exclude each other: a
+// setter refuses while another mode is on, and the per-rank and stage entry points serve plain
+// contexts (frm_render_shutter: supersampled ones too). frame_mode() derives it from the setters'
+// fields, which stay because the getters return them and their "off" values are kept state.
+enum FrameMode : uint8_t { kPlain, kSupersampled, kAdaptive, kPanorama, kDof };
+// A mode for refuse_mode(): "a <noun> context (<setter>); <instead>".
+struct ModeText {
+  const char *noun, *setter, *instead;
+};
+static constexpr ModeText kModeText[] = {
+    {"plain", "", ""},
+    {"supersampled", "frm_set_supersampling",
+     "switch that off, or render the bands at the internal size on a plain context and call frm_resolve"},
+    {"adaptive", "frm_set_adaptive", "switch that off, or render the bands on a plain context and call frm_refine"},
+    {"panorama", "frm_set_panorama",
+     "switch that off, or render the faces (frm_panorama_parameters) on a plain context and call frm_project_equirect"},
+    {"depth-of-field", "frm_set_depth_of_field",
+     "switch that off, or render on a plain context and call frm_depth_of_field"},
+};
+
 // A device buffer of a context's pool (frm_ctx::pool) that follows the frame size: grown on demand
 // (pool_grow), a smaller need keeps the larger block. Pointer and capacity change together.
 struct PoolBuf {
@@ -79,10 +99,15 @@ struct Slot {
   // supersampling (frm_set_supersampling, factor > 1): the resolved image of fbs[i], what the
   // presentation paths read; alternating with the framebuffers, so fb_read[i] covers its readers too
   PoolBuf res[2];
-  // adaptive supersampling (frm_set_adaptive, factor > 1): res[i] holds the adaptive frame of fbs[i]
-  // (adaptive[i]: the slot's last frm_render into fbs[i] was adaptive), and the slot's scratch of
-  // the pass: the list of refined pixels (one u32 per pixel) and its control words
-  bool adaptive[2] = {false, false};
+  // what res[i] holds of the slot's last frame into fbs[i]: its resolve, its adaptive or its gathered
+  // frame (the FrameMode that frame was rendered in), kPlain: nothing, the frame is fbs[i] itself
+  uint8_t second[2] = {kPlain, kPlain};
+  void no_second(bool both = false) {
+    second[fb_idx] = kPlain;
+    if (both) second[fb_idx ^ 1u] = kPlain;
+  }
+  // adaptive supersampling (frm_set_adaptive, factor > 1): the slot's scratch of the pass: the list of
+  // refined pixels (one u32 per pixel) and its control words
   PoolBuf refine_list;
   uint32_t* refine_ctl = nullptr;
   uint32_t refine_w = 0, refine_h = 0;  // the frame the list belongs to
@@ -93,10 +118,8 @@ struct Slot {
   // (equirect_tables) of a pano_w x pano_h output, uploaded when the output size changes
   PoolBuf pano_src, pano_tables;
   uint32_t pano_w = 0, pano_h = 0;
-  // depth of field (frm_set_depth_of_field): res[i] holds the gathered frame of fbs[i] (dof[i]: the
-  // slot's last frm_render into fbs[i] was gathered) and `depth` the plane of the slot's last such
-  // frame, depth_w x depth_h floats (frm_read_depth)
-  bool dof[2] = {false, false};
+  // depth of field (frm_set_depth_of_field): the plane of the slot's last gathered frame, depth_w x
+  // depth_h floats (frm_read_depth)
   PoolBuf depth;
   uint32_t depth_w = 0, depth_h = 0;
   unsigned int* queue = nullptr;
@@ -253,9 +276,11 @@ struct frm_ctx {
   bool has_params = false;
   SceneUniforms scene{};
   uint32_t shutter_chunk = FRM_MAX_SHUTTER_SAMPLES;  // frm_render_shutter: sub-frames per chunk at most (FRM_SHUTTER_CHUNK)
-  uint64_t shutter_seq = 0;  // render_seq of the last frm_render_shutter (0: none)
+  // the last frame composed of several (frm_render_shutter's sub-frames, a panorama's faces), which
+  // leaves no single frame to trace: its render_seq (0: none) and what it was made of
+  uint64_t composed_seq = 0;
+  const char* composed_of = "";
   uint32_t panorama = 0;      // frm_set_panorama: the face size N (0: off); the render size is (N + 2)^2
-  uint64_t panorama_seq = 0;  // render_seq of the last panorama frm_render (0: none)
   uint32_t dof_radius = 0;  // frm_set_depth_of_field: the largest radius R (0: off)
   float dof_aperture = 0.0f, dof_focus = 1.0f;
   // host copies of direction tables whose upload may still be running: each is released once the
@@ -287,12 +312,39 @@ struct frm_ctx {
 // render-texture steps (4 % per axis), which then reuse the block.
 static inline size_t with_headroom(size_t bytes) { return bytes + bytes / 4u; }
 
+static inline FrameMode frame_mode(const frm_ctx* ctx) {
+  if (ctx->dof_radius) return kDof;
+  if (ctx->panorama) return kPanorama;
+  if (ctx->adaptive > 1u) return kAdaptive;
+  return ctx->supersample > 1u ? kSupersampled : kPlain;
+}
+
+// The frames of one multi-frame launch may differ in camera, and for the Mandelbulb in time (its
+// power, fragment.wgsl:75, is the only time-derived constant): otherwise the same scene uniforms
+// (scene, iterations, time-derived constants). s0: frame 0's uniforms, powers[k]: frame k's power,
+// anim: the powers differ, differs: the first frame whose uniforms differ from frame 0's in more
+// than that (0: none).
+struct BatchUniforms {
+  SceneUniforms s0;
+  float powers[FRM_MAX_BATCH];
+  bool anim;
+  uint32_t differs;
+};
+
 // The host layer's own functions stay out of libfrm.so's dynamic symbols.
 #pragma GCC visibility push(hidden)
 // frm_api.hip
 int fail(frm_ctx* ctx, int code, const char* fmt, ...);
 int hip_fail(frm_ctx* ctx, hipError_t e, const char* what);
 int create_one(const frm_config* config, int device, frm_ctx** out_ctx);
+int not_on_group(frm_ctx* ctx, const char* what);
+int refuse_mode(frm_ctx* ctx, const char* what);
+int ensure_ready(frm_ctx* ctx);
+int check_parameters(frm_ctx* ctx, const SceneUniforms& su, const frm_parameters& p);
+// frm_stages.hip
+int check_size(frm_ctx* ctx, uint32_t width, uint32_t height, uint32_t factor, const char* noun);
+int check_output(frm_ctx* ctx, uint32_t out_width, uint32_t out_height, uint32_t flags);
+int check_lens(frm_ctx* ctx, float aperture, float focus, uint32_t max_radius);
 // frm_launch.hip
 int dev_alloc(frm_ctx* ctx, void** p, size_t bytes, hipStream_t s);
 int dev_release(frm_ctx* ctx, void* p, hipStream_t s);
@@ -317,9 +369,15 @@ int wait_slot(frm_ctx* ctx, Slot& sl);
 int synchronize_all(frm_ctx* ctx);
 int slot_stream(frm_ctx* ctx, uint32_t i, hipStream_t* out);
 int launch(frm_ctx* ctx, KernelArgs a, hipStream_t s);
+void batch_uniforms(const frm_ctx* ctx, uint32_t count, const frm_parameters* params, BatchUniforms* u);
+int launch_frames(frm_ctx* ctx, uint32_t count, const frm_parameters* params, const BatchUniforms& u,
+                  bool scene_per_frame, uint8_t* dst, size_t frame_stride_bytes, const BandGeometry& g,
+                  unsigned long long* counters, hipStream_t s, int pin_slot);
+int frame_prologue(frm_ctx* ctx, const frm_stats* stats);
 int begin_frame(frm_ctx* ctx, Slot** out_slot, hipStream_t* out_stream);
 int stats_begin(frm_ctx* ctx, hipStream_t s);
 int stats_end(frm_ctx* ctx, hipStream_t s, uint64_t* out_counters, float* out_ms);
+int finish_stats(frm_ctx* ctx, hipStream_t s, frm_stats* stats);
 void show_slot(frm_ctx* ctx, const Slot& sl);
 void keep_render_params(frm_ctx* ctx);
 // frm_group.hip

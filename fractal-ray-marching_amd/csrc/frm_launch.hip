@@ -1,5 +1,6 @@
 // frm_launch.hip — what every render path of a context shares: the pool buffers that follow the
-// frame size, slot framebuffers and streams, a launch's arguments, launch(), the steps of a frame.
+// frame size, slot framebuffers and streams, a launch's arguments, launch(), several frames in one
+// launch (launch_frames), the steps of a frame.
 #include "frm_ctx.h"
 
 // Device memory of the context pool, allocated / released in the order of stream s: a block
@@ -121,11 +122,12 @@ int ensure_panorama(frm_ctx* ctx, Slot& sl, size_t src_bytes, uint32_t w, uint32
 // launch wrote the records of this slot). The slot's `done` event is recorded again, so that it
 // covers it.
 int resolve_frame(frm_ctx* ctx, Slot& sl) {
-  sl.adaptive[sl.fb_idx] = sl.dof[sl.fb_idx] = false;
-  if (ctx->supersample == 1u && ctx->adaptive == 1u && ctx->dof_radius == 0u) return FRM_OK;
+  sl.no_second();
+  const FrameMode mode = frame_mode(ctx);
+  if (mode == kPlain || mode == kPanorama) return FRM_OK;  // (a panorama is projected into the framebuffer)
   if (int rc = ensure_res(ctx, sl, (size_t)ctx->out_width * ctx->out_height * 4u)) return rc;
   uint8_t* res = sl.res[sl.fb_idx].p;
-  if (ctx->dof_radius) {  // (excludes supersampling and the adaptive pass: the render size is the output size)
+  if (mode == kDof) {  // (the render size is the output size)
     const size_t npix = (size_t)ctx->width * ctx->height;
     if (!sl.records.p || sl.records.cap < npix * kRecordBytes)
       return fail(ctx, FRM_ERR_HIP, "depth of field: the frame left no records in its slot");
@@ -135,28 +137,28 @@ int resolve_frame(frm_ctx* ctx, Slot& sl) {
                               (float*)sl.depth.p, (uint32_t)npix, sl.stream));
     FRM_HIP(ctx, launch_dof(sl.fb(), (const float*)sl.depth.p, res, ctx->width, ctx->height, ctx->dof_aperture,
                             ctx->dof_focus, ctx->dof_radius, sl.stream));
-    sl.dof[sl.fb_idx] = true;
     sl.depth_w = ctx->width;
     sl.depth_h = ctx->height;
-  } else if (ctx->adaptive > 1u) {  // (excludes supersampling: the render size is the output size)
+  } else if (mode == kAdaptive) {  // (the render size is the output size)
     if (int rc = ensure_refine(ctx, sl, (size_t)ctx->width * ctx->height)) return rc;
     FrameUniforms f;
     compute_frame_uniforms(ctx->params, ctx->adaptive * ctx->width, ctx->adaptive * ctx->height, ctx->max_steps, &f);
     FRM_HIP(ctx, launch_adaptive(f, ctx->scene, sl.fb(), res, ctx->width, ctx->height, ctx->adaptive,
                                  ctx->edge_threshold, (uint32_t*)sl.refine_list.p, sl.refine_ctl, ctx->counters,
                                  ctx->cu_count, sl.stream));
-    sl.adaptive[sl.fb_idx] = true;
     sl.refine_w = ctx->width;
     sl.refine_h = ctx->height;
   } else {
     FRM_HIP(ctx, launch_resolve(sl.fb(), res, ctx->out_width, ctx->out_height, ctx->supersample, sl.stream));
   }
+  sl.second[sl.fb_idx] = mode;
   FRM_HIP(ctx, hipEventRecord(sl.done, sl.stream));
   return FRM_OK;
 }
-// What the presentation paths read of a slot: out_width x out_height texels.
+// What the presentation paths read of a slot: out_width x out_height texels. Supersampling is the
+// context's, not the slot's: apply_size sizes the resolved image before the first render.
 const uint8_t* shown(const frm_ctx* ctx, const Slot& sl) {
-  return ctx->supersample > 1u || sl.adaptive[sl.fb_idx] || sl.dof[sl.fb_idx] ? sl.res[sl.fb_idx].p : sl.fb();
+  return ctx->supersample > 1u || sl.second[sl.fb_idx] != kPlain ? sl.res[sl.fb_idx].p : sl.fb();
 }
 
 static uint32_t num_bands(uint32_t height, uint32_t band_rows) { return (height + band_rows - 1) / band_rows; }
@@ -214,7 +216,7 @@ KernelArgs make_args(const frm_ctx* ctx, const frm_parameters& params, const Sce
 KernelKind kernel_for(const frm_ctx* ctx, uint64_t pixels) {
   if (ctx->flags & FRM_FLAG_SIMPLE_KERNEL) return kKernelSimple;
   if (ctx->flags & FRM_FLAG_PERSISTENT_KERNEL) return kKernelPersistent;
-  if (ctx->dof_radius) return kKernelPersistent;  // the depth plane comes from its records (same bytes)
+  if (frame_mode(ctx) == kDof) return kKernelPersistent;  // the depth plane comes from its records (same bytes)
   return pixels < kSimplePixelsPerCu * (uint64_t)ctx->cu_count ? kKernelSimple : kKernelPersistent;
 }
 
@@ -424,7 +426,82 @@ int launch(frm_ctx* ctx, KernelArgs a, hipStream_t s) {
   return FRM_OK;
 }
 
+// ---- several frames of the context's size, one launch if possible ------------------------------
+// (frm_render_bands_batch's frames, a chunk of frm_render_shutter's sub-frames, a panorama's faces)
+
+void batch_uniforms(const frm_ctx* ctx, uint32_t count, const frm_parameters* params, BatchUniforms* u) {
+  compute_scene_uniforms(params[0], ctx->flags, &u->s0);
+  u->anim = false;
+  u->differs = 0;
+  u->powers[0] = u->s0.mb_power;
+  for (uint32_t k = 1; k < count && !u->differs; ++k) {
+    SceneUniforms sk;
+    compute_scene_uniforms(params[k], ctx->flags, &sk);
+    u->powers[k] = sk.mb_power;
+    if (is_mandelbulb(u->s0.family) && sk.family == u->s0.family && sk.mb_power != u->s0.mb_power) {
+      u->anim = true;
+      sk.mb_power = u->s0.mb_power;
+      sk.mb_power_m1 = u->s0.mb_power_m1;
+    }
+    if (memcmp(&u->s0, &sk, sizeof(sk)) != 0) u->differs = k;
+  }
+}
+// Whether `count` such frames of a.npix local pixels share one launch; else one launch per frame:
+// the simple kernel has no queue to share; runtime-reloaded modules carry the single-frame kernels
+// only; per-frame powers need the Mandelbulb's N >= 1 kernels.
+static bool batch_shares_launch(const frm_ctx* ctx, const KernelArgs& a, uint32_t count, bool anim) {
+  return !(count == 1 || kernel_for(ctx, a.npix) == kKernelSimple || ctx->reloaded || (anim && a.s.n == 0));
+}
+// Makes `a` (make_args of any of the frames) the shared launch of the `count` frames, frame k written
+// frame_stride_bytes after frame k - 1.
+static void set_batch(const frm_ctx* ctx, KernelArgs& a, uint32_t count, const frm_parameters* params,
+                      const float* powers, bool anim, size_t frame_stride_bytes) {
+  a.batch = count;
+  a.out_stride = (uint32_t)(frame_stride_bytes / 4u);
+  a.anim = anim ? 1u : 0u;
+  memcpy(a.mb_powers, powers, sizeof(float) * count);
+  FrameUniforms fk;
+  for (uint32_t k = 0; k < count; ++k) {
+    compute_frame_uniforms(params[k], ctx->width, ctx->height, ctx->max_steps, &fk);
+    memcpy(a.cams[k].row, fk.row, sizeof(fk.row));
+    a.cams[k].origin = fk.origin;
+  }
+}
+// Renders the `count` frames of params (u: their batch_uniforms) on stream s, bands g of frame k at
+// dst + k * frame_stride_bytes: in one launch when the frames differ in no more than a launch can
+// carry and the kernel can share (batch_shares_launch), else one launch per frame, each with its own
+// scene uniforms (scene_per_frame) or all with frame 0's (frames that differ in their cameras
+// alone). pin_slot >= 0: every launch runs on that slot (launch() takes the context's next one and
+// moves on: a frame of several launches stays on its slot).
+int launch_frames(frm_ctx* ctx, uint32_t count, const frm_parameters* params, const BatchUniforms& u,
+                  bool scene_per_frame, uint8_t* dst, size_t frame_stride_bytes, const BandGeometry& g,
+                  unsigned long long* counters, hipStream_t s, int pin_slot) {
+  KernelArgs a = make_args(ctx, params[0], u.s0, dst, counters, g.band_rows, g.first_band, g.band_stride, g.local_rows);
+  const bool shared = !u.differs && batch_shares_launch(ctx, a, count, u.anim);
+  if (shared) set_batch(ctx, a, count, params, u.powers, u.anim, frame_stride_bytes);
+  for (uint32_t k = 0; k < (shared ? 1u : count); ++k) {
+    if (!shared) {
+      SceneUniforms sk = u.s0;
+      if (scene_per_frame) compute_scene_uniforms(params[k], ctx->flags, &sk);
+      a = make_args(ctx, params[k], sk, dst + (size_t)k * frame_stride_bytes, counters, g.band_rows, g.first_band,
+                    g.band_stride, g.local_rows);
+    }
+    if (pin_slot >= 0) ctx->next_slot = (uint32_t)pin_slot;
+    if (int rc = launch(ctx, a, s)) return rc;
+  }
+  return FRM_OK;
+}
+
 // ---- the steps of a frame (frm_render, group_render; the ring writes the last two) ----------
+
+// Before a frame outside the ring, on the context's device: the ring's frames first, and for a frame
+// with stats every slot drained (the counters must hold this frame alone).
+int frame_prologue(frm_ctx* ctx, const frm_stats* stats) {
+  FRM_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = ring_quiesce(ctx)) return rc;
+  ctx->last_is_ring = false;
+  return stats ? synchronize_all(ctx) : FRM_OK;
+}
 
 // Claims the context's next slot for a frame of the context's size: its stream, and the other
 // framebuffer of the slot: the last one may still be read back (copy stream); this one's readback
@@ -451,6 +528,16 @@ int stats_end(frm_ctx* ctx, hipStream_t s, uint64_t* out_counters, float* out_ms
   FRM_HIP(ctx, hipMemcpyAsync(out_counters, ctx->counters, FRM_NUM_COUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   FRM_HIP(ctx, hipStreamSynchronize(s));
   FRM_HIP(ctx, hipEventElapsedTime(out_ms, ctx->ev_start, ctx->ev_stop));
+  return FRM_OK;
+}
+// The end of a single-device frame: nothing without stats, else stats_end into *stats.
+int finish_stats(frm_ctx* ctx, hipStream_t s, frm_stats* stats) {
+  if (!stats) return FRM_OK;
+  uint64_t host[FRM_NUM_COUNTERS];
+  float ms = 0.0f;
+  int rc = stats_end(ctx, s, host, &ms);
+  if (rc || (rc = frm_stats_from_counters(ctx, host, stats))) return rc;
+  stats->kernel_ms = ms;
   return FRM_OK;
 }
 

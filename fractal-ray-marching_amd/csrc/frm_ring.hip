@@ -18,7 +18,7 @@ static uint32_t ring_size(const frm_ctx* ctx) { return ctx->nslots >= 3 ? 4u : 2
 // Whether frm_render(ctx, NULL) goes through the ring.
 bool ring_eligible(const frm_ctx* ctx) {
   if (!ctx->ring_enabled || ctx->group || ctx->bands_only || ctx->reloaded || ctx->nslots < 2) return false;
-  if (ctx->supersample > 1u || ctx->adaptive > 1u || ctx->dof_radius) return false;  // ring frames are not resolved, refined or gathered
+  if (frame_mode(ctx) != kPlain) return false;  // ring frames are not resolved, refined, gathered or projected
   const uint64_t npix = (uint64_t)ctx->width * ctx->height;
   if (kernel_for(ctx, npix) != kKernelPersistent || npix > (1ull << 28)) return false;
   // a ring's service waves give up after kRingWatchdogTicks (2 s) without progress: keep the
@@ -259,7 +259,7 @@ int ring_materialize(frm_ctx* ctx) {
   const size_t bytes = (size_t)ctx->width * ctx->height * 4u;
   if ((rc = select_fb(ctx, sl, sl.fb_idx)) || (rc = ensure_fb(ctx, sl, bytes))) return rc;
   const uint32_t s = (R.last_seq - 1u) & (R.slots - 1u);
-  sl.adaptive[sl.fb_idx] = sl.dof[sl.fb_idx] = false;
+  sl.no_second();
   FRM_HIP(ctx, hipMemcpyAsync(sl.fb(), R.out + (size_t)s * R.w * R.h, bytes, hipMemcpyDeviceToDevice, ctx->stream));
   FRM_HIP(ctx, hipEventRecord(sl.done, ctx->stream));
   sl.pending = true;

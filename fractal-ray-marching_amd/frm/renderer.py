@@ -194,9 +194,7 @@ class Renderer:
         rendered with params_list (1..FRM_MAX_SHUTTER_SAMPLES Parameters of one scene, e.g. from
         frm.shutter_parameters); the context's parameters become the last. Returns frm_stats summed
         over the sub-frames as a dict when stats=True."""
-        arr = (_lib.FrmParameters * max(1, len(params_list)))()
-        for k, p in enumerate(params_list):
-            ctypes.memmove(ctypes.addressof(arr[k]), p.to_bytes(), ctypes.sizeof(_lib.FrmParameters))
+        arr = _params_array(params_list)
         st = _lib.FrmStats() if stats else None
         self._check(self._lib.frm_render_shutter(self.ctx, len(params_list), ctypes.addressof(arr),
                                                  ctypes.byref(st) if stats else None))
@@ -221,7 +219,7 @@ class Renderer:
     # blit.wgsl + present (graphics.rs:91-110): the frame resampled to a window size
     def present(self, width, height, srgb=True, bgra=False):
         buf = np.empty((height, width, 4), dtype=np.uint8)
-        flags = (_lib.FRM_BLIT_SRGB if srgb else 0) | (_lib.FRM_BLIT_BGRA if bgra else 0)
+        flags = _blit_flags(srgb, bgra)
         self._check(self._lib.frm_present(self.ctx, width, height, flags, buf.ctypes.data, buf.nbytes))
         return buf
 
@@ -229,7 +227,7 @@ class Renderer:
              stream=0):
         """frm_blit: present()'s resample of src_h x src_w RGBA8 sRGB texels at device pointer src_ptr
         into out_h x out_w at dst_ptr, asynchronously on `stream` (0: the context's)."""
-        flags = (_lib.FRM_BLIT_SRGB if srgb else 0) | (_lib.FRM_BLIT_BGRA if bgra else 0)
+        flags = _blit_flags(srgb, bgra)
         self._check(self._lib.frm_blit(self.ctx, src_ptr, src_bytes, src_w, src_h, dst_ptr, dst_bytes, out_w, out_h,
                                        flags, stream or None))
 
@@ -243,7 +241,7 @@ class Renderer:
 
     def present_async(self, width, height, srgb=True, bgra=False):
         t = ctypes.c_uint64()
-        flags = (_lib.FRM_BLIT_SRGB if srgb else 0) | (_lib.FRM_BLIT_BGRA if bgra else 0)
+        flags = _blit_flags(srgb, bgra)
         self._check(self._lib.frm_present_async(self.ctx, width, height, flags, ctypes.byref(t)))
         return self._remember(t.value, (height, width, 4))
 
@@ -305,10 +303,7 @@ class Renderer:
         one launch, frame k at dev_ptr + k * frame_stride; dst_bytes = the size of the buffer at
         dev_ptr (the library checks every frame against it: pass the real allocation, e.g.
         tensor.numel(), never a size derived from the stride)."""
-        from ._lib import FrmParameters
-        arr = (FrmParameters * len(params_list))()
-        for k, p in enumerate(params_list):
-            ctypes.memmove(ctypes.addressof(arr[k]), p.to_bytes(), ctypes.sizeof(FrmParameters))
+        arr = _params_array(params_list)
         self._check(self._lib.frm_render_bands_batch(self.ctx, len(params_list), ctypes.addressof(arr), dev_ptr,
                                                      dst_bytes, frame_stride, band_rows, first_band, band_stride,
                                                      stream or None, dev_counters or None))
@@ -390,6 +385,18 @@ class Renderer:
         st = _lib.FrmStats()
         self._check(self._lib.frm_stats_from_counters(self.ctx, arr, ctypes.byref(st)))
         return st.as_dict()
+
+
+def _params_array(params_list):
+    """The Parameters of params_list as one C array (at least one element long)."""
+    arr = (_lib.FrmParameters * max(1, len(params_list)))()
+    for k, p in enumerate(params_list):
+        ctypes.memmove(ctypes.addressof(arr[k]), p.to_bytes(), ctypes.sizeof(_lib.FrmParameters))
+    return arr
+
+
+def _blit_flags(srgb, bgra):
+    return (_lib.FRM_BLIT_SRGB if srgb else 0) | (_lib.FRM_BLIT_BGRA if bgra else 0)
 
 
 def device_count():
