@@ -606,10 +606,14 @@ int frm_render_bands(frm_ctx* ctx, uint8_t* dev_dst, size_t dst_bytes, uint32_t 
   if (frame_mode(ctx) != kPlain) return refuse_mode(ctx, "frm_render_bands");
   if (!dev_dst || band_rows == 0 || band_stride == 0)
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "invalid dst or band geometry");
-  uint32_t rows = band_local_rows(ctx->height, band_rows, first_band, band_stride);
+  uint32_t rows = 0;
+  if ((rc = band_rows_u32(ctx, ctx->height, band_rows, first_band, band_stride, &rows))) return rc;
   size_t need = (size_t)rows * ctx->width * 4u;
   if (dst_bytes < need)
     return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "dst holds %zu bytes, bands need %zu", dst_bytes, need);
+  if ((rc = check_spans(ctx, {{"dev_dst", dev_dst, dst_bytes, need, 4, true},
+                              {"dev_counters", dev_counters, 0, 0, 8, true}})))
+    return rc;
   FRM_HIP(ctx, hipSetDevice(ctx->device));
   if ((rc = ring_leave(ctx))) return rc;
   hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
@@ -629,7 +633,8 @@ int frm_render_bands_batch(frm_ctx* ctx, uint32_t count, const frm_parameters* p
   if (!params || !dev_dst || count == 0 || count > FRM_MAX_BATCH || band_rows == 0 || band_stride == 0)
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "invalid batch (count %u, at most %u) or band geometry", count,
                 FRM_MAX_BATCH);
-  const uint32_t rows = band_local_rows(ctx->height, band_rows, first_band, band_stride);
+  uint32_t rows = 0;
+  if (int rc = band_rows_u32(ctx, ctx->height, band_rows, first_band, band_stride, &rows)) return rc;
   const size_t need = (size_t)rows * ctx->width * 4u;
   if (frame_stride_bytes < need || frame_stride_bytes % 4u || frame_stride_bytes / 4u > 0xFFFFFFFFull)
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT,
@@ -658,6 +663,10 @@ int frm_render_bands_batch(frm_ctx* ctx, uint32_t count, const frm_parameters* p
                 "batch frame %u differs from frame 0 in more than the camera and the Mandelbulb's time "
                 "(scene, iterations, time-derived constants, aspect)",
                 differs);
+  // (the sizes were checked above: what is left of the one span check is the alignment)
+  if (int rc = check_spans(ctx, {{"dev_dst", dev_dst, dst_bytes, need ? (count - 1u) * frame_stride_bytes + need : 0, 4, true},
+                                 {"dev_counters", dev_counters, 0, 0, 8, true}}))
+    return rc;
   FRM_HIP(ctx, hipSetDevice(ctx->device));
   if (int rc = ring_leave(ctx)) return rc;
   ctx->params = params[count - 1];  // the context's parameters: the batch's last frame

@@ -11,6 +11,7 @@
 
 #include <sched.h>
 
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <vector>
@@ -331,6 +332,17 @@ struct BatchUniforms {
   uint32_t differs;
 };
 
+// A device buffer of a stage or band entry point, for check_spans: the argument's name, the bytes the
+// caller says it holds and the bytes the call touches (0: the buffer is not used, and may be NULL),
+// its alignment, and whether the call writes it.
+struct Span {
+  const char* name;
+  const void* p;
+  size_t held, need;
+  uint32_t align;
+  bool written;
+};
+
 // The host layer's own functions stay out of libfrm.so's dynamic symbols.
 #pragma GCC visibility push(hidden)
 // frm_api.hip
@@ -345,6 +357,7 @@ int check_parameters(frm_ctx* ctx, const SceneUniforms& su, const frm_parameters
 int check_size(frm_ctx* ctx, uint32_t width, uint32_t height, uint32_t factor, const char* noun);
 int check_output(frm_ctx* ctx, uint32_t out_width, uint32_t out_height, uint32_t flags);
 int check_lens(frm_ctx* ctx, float aperture, float focus, uint32_t max_radius);
+int check_spans(frm_ctx* ctx, std::initializer_list<Span> spans);
 // frm_launch.hip
 int dev_alloc(frm_ctx* ctx, void** p, size_t bytes, hipStream_t s);
 int dev_release(frm_ctx* ctx, void* p, hipStream_t s);
@@ -359,7 +372,9 @@ int upload_tables(frm_ctx* ctx, float* dev, uint32_t w, uint32_t h, hipStream_t 
 void release_host_blocks(frm_ctx* ctx, bool wait);
 int ensure_panorama(frm_ctx* ctx, Slot& sl, size_t src_bytes, uint32_t w, uint32_t h);
 const uint8_t* shown(const frm_ctx* ctx, const Slot& sl);
-uint32_t band_local_rows(uint32_t height, uint32_t band_rows, uint32_t first, uint32_t stride);
+uint32_t num_bands(uint32_t height, uint32_t band_rows);
+uint64_t band_local_rows(uint32_t height, uint32_t band_rows, uint32_t first, uint32_t stride);
+int band_rows_u32(frm_ctx* ctx, uint32_t height, uint32_t band_rows, uint32_t first, uint32_t stride, uint32_t* rows);
 uint32_t group_band_rows(uint32_t height, uint32_t n);
 KernelArgs make_args(const frm_ctx* ctx, const frm_parameters& params, const SceneUniforms& scene, uint8_t* dst,
                      unsigned long long* counters, uint32_t band_rows, uint32_t first, uint32_t stride,

@@ -109,7 +109,7 @@ int group_render(frm_ctx* ctx, frm_stats* stats) {
   if ((rc = pool_grow(ctx, gs.gathered, (size_t)n * G.stride, s0))) return rc;
   if (stats && (rc = stats_begin(ctx, s0))) return rc;
   uint32_t rows[FRM_MAX_DEVICES];
-  for (uint32_t r = 0; r < n; ++r) rows[r] = band_local_rows(ctx->height, G.band_rows, r, n);
+  for (uint32_t r = 0; r < n; ++r) rows[r] = (uint32_t)band_local_rows(ctx->height, G.band_rows, r, n);  // below height + band_rows
   // ranks 1..n-1 on their devices
   for (uint32_t r = 1; r < n; ++r) {
     frm_ctx* c = G.sub[r];

@@ -503,7 +503,11 @@ hipError_t launch_resolve(const uint8_t* src, uint8_t* dst, uint32_t dw, uint32_
 hipError_t launch_unshuffle(const uint8_t* src, size_t rank_stride, uint8_t* dst, uint32_t width,
                             uint32_t height, uint32_t band_rows, uint32_t ranks,
                             hipStream_t stream) {
-  if (width % 4u == 0 && rank_stride % 16u == 0) {
+  // uint4 words only where every row of src and dst starts on 16 bytes: rows and rank strides of
+  // 16-byte multiples from 16-byte aligned pointers (a caller's may be 4-byte aligned: dwords then)
+  const bool vec = width % 4u == 0 && rank_stride % 16u == 0 &&
+                   (reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) % 16u == 0;
+  if (vec) {
     const uint32_t words = width / 4u;
     dim3 grid((words + 255u) / 256u, height);
     hipLaunchKernelGGL(unshuffle_bands<uint4>, grid, dim3(256), 0, stream, (const uint4*)src,

@@ -161,15 +161,28 @@ const uint8_t* shown(const frm_ctx* ctx, const Slot& sl) {
   return ctx->supersample > 1u || sl.second[sl.fb_idx] != kPlain ? sl.res[sl.fb_idx].p : sl.fb();
 }
 
-static uint32_t num_bands(uint32_t height, uint32_t band_rows) { return (height + band_rows - 1) / band_rows; }
+// Bands of a frame of height >= 1 rows: ceil(height / band_rows), without the sum height + band_rows
+// - 1, which wraps for band_rows near 2^32 (one band would count as none).
+uint32_t num_bands(uint32_t height, uint32_t band_rows) { return (height - 1u) / band_rows + 1u; }
 
 // Rows produced by bands first, first+stride, ... below num_bands (the last band of the
-// frame may be short, but a band buffer always reserves band_rows rows for it).
-uint32_t band_local_rows(uint32_t height, uint32_t band_rows, uint32_t first, uint32_t stride) {
+// frame may be short, but a band buffer always reserves band_rows rows for it). In 64 bits: the
+// count is below height + band_rows, which 32 bits need not hold.
+uint64_t band_local_rows(uint32_t height, uint32_t band_rows, uint32_t first, uint32_t stride) {
   uint32_t nb = num_bands(height, band_rows);
   if (first >= nb) return 0;
   uint32_t count = (nb - 1 - first) / stride + 1;
-  return count * band_rows;
+  return (uint64_t)count * band_rows;
+}
+// band_local_rows as the 32 bits a launch and *out_rows hold: refused, *rows left alone, when it
+// does not fit (only a height above FRM_MAX_DIMENSION can get there: a context's rows always fit).
+int band_rows_u32(frm_ctx* ctx, uint32_t height, uint32_t band_rows, uint32_t first, uint32_t stride, uint32_t* rows) {
+  const uint64_t r = band_local_rows(height, band_rows, first, stride);
+  if (r > 0xFFFFFFFFull)
+    return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "bands of %u rows of a frame of %u rows: %llu rows do not fit 32 bits",
+                band_rows, height, (unsigned long long)r);
+  *rows = (uint32_t)r;
+  return FRM_OK;
 }
 
 // Local rows that hold frame rows: all but the missing rows of a short last band, which

@@ -4,8 +4,6 @@
 // helpers that go with them, and the one check of their buffers.
 #include "frm_ctx.h"
 
-#include <initializer_list>
-
 // A frame size for `factor` samples per pixel and axis: [1, FRM_MAX_DIMENSION / factor]^2.
 int check_size(frm_ctx* ctx, uint32_t width, uint32_t height, uint32_t factor, const char* noun) {
   const uint32_t limit = FRM_MAX_DIMENSION / factor;
@@ -33,21 +31,9 @@ int check_lens(frm_ctx* ctx, float aperture, float focus, uint32_t max_radius) {
   return FRM_OK;
 }
 
-namespace {
-
-// A device buffer of a stage: the argument's name, the bytes the caller says it holds and the bytes
-// the call touches (0: the buffer is not used, and may be NULL), its alignment, and whether the
-// stage writes it.
-struct Span {
-  const char* name;
-  const void* p;
-  size_t held, need;
-  uint32_t align;
-  bool written;
-};
-
-// The buffers of one call, reported in this order: every alignment, then every size in list order,
-// then every pair that overlaps with one of the two written (two inputs may share bytes).
+// The buffers (frm_ctx.h Span) of one call, reported in this order: every alignment, then every size
+// in list order, then every pair that overlaps with one of the two written (two inputs may share
+// bytes). The band entry points of frm_api.hip check theirs here too.
 int check_spans(frm_ctx* ctx, std::initializer_list<Span> spans) {
   for (const Span& s : spans)
     if (reinterpret_cast<uintptr_t>(s.p) % s.align)
@@ -63,6 +49,8 @@ int check_spans(frm_ctx* ctx, std::initializer_list<Span> spans) {
     }
   return FRM_OK;
 }
+
+namespace {
 
 // *need: the bytes that `count` frames of frame_need bytes, stride bytes apart, span (SIZE_MAX: more
 // than any buffer holds). A stride below a frame or not a multiple of 4 is refused.
@@ -272,8 +260,7 @@ int frm_band_rows_for(uint32_t height, uint32_t band_rows, uint32_t first_band, 
                       uint32_t* out_rows) {
   if (!out_rows || height == 0 || band_rows == 0 || band_stride == 0)
     return fail(nullptr, FRM_ERR_INVALID_ARGUMENT, "invalid band geometry");
-  *out_rows = band_local_rows(height, band_rows, first_band, band_stride);
-  return FRM_OK;
+  return band_rows_u32(nullptr, height, band_rows, first_band, band_stride, out_rows);
 }
 
 int frm_unshuffle_bands(frm_ctx* ctx, const uint8_t* dev_src, size_t rank_stride_bytes, uint8_t* dev_dst,
@@ -285,11 +272,22 @@ int frm_unshuffle_bands(frm_ctx* ctx, const uint8_t* dev_src, size_t rank_stride
   size_t need = (size_t)ctx->width * ctx->height * 4u;
   if (dst_bytes < need)
     return fail(ctx, FRM_ERR_BUFFER_TOO_SMALL, "dst holds %zu bytes, frame needs %zu", dst_bytes, need);
-  uint32_t rows = band_local_rows(ctx->height, band_rows, 0, ranks);
+  uint32_t rows = 0;
+  if (int rc = band_rows_u32(ctx, ctx->height, band_rows, 0, ranks, &rows)) return rc;
   if (rank_stride_bytes < (size_t)rows * ctx->width * 4u)
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "rank stride %zu below one rank's bands", rank_stride_bytes);
   if (rank_stride_bytes % 4u)
     return fail(ctx, FRM_ERR_INVALID_ARGUMENT, "rank stride must be a multiple of 4");
+  // what the call reads of dev_src: from its start to the end of the rows of the last rank that holds
+  // a band (the ranks beyond the frame's bands are never touched)
+  const uint32_t nb = num_bands(ctx->height, band_rows), holders = ranks < nb ? ranks : nb;
+  uint32_t last_rows = 0;
+  if (int rc = band_rows_u32(ctx, ctx->height, band_rows, holders - 1u, ranks, &last_rows)) return rc;
+  size_t src_need = 0;
+  if (int rc = strided_need(ctx, rank_stride_bytes, (size_t)last_rows * ctx->width * 4u, holders, &src_need)) return rc;
+  if (int rc = check_spans(ctx, {{"dev_src", dev_src, src_need, src_need, 4, false},
+                                 {"dev_dst", dev_dst, dst_bytes, need, 4, true}}))
+    return rc;
   FRM_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
   FRM_HIP(ctx, launch_unshuffle(dev_src, rank_stride_bytes, dev_dst, ctx->width, ctx->height, band_rows,

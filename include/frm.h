@@ -355,7 +355,18 @@ int frm_reload(frm_ctx* ctx, const char* source_dir);
  *      memory of FRM_NUM_COUNTERS uint64 to which the work counters are ADDED.
  *      Asynchronous. With frames_in_flight = F the launch uses the next of F scratch
  *      slots; a slot last used on another stream is awaited on the device, so a caller
- *      that rotates F streams (and F destination buffers) overlaps F launches. */
+ *      that rotates F streams (and F destination buffers) overlaps F launches.
+ * frm_band_rows_for: the rows such a call stores for a frame of `height` rows: whole bands, a
+ *      short last band of the frame counted as band_rows rows (0 when first_band is at or beyond
+ *      the band count). FRM_ERR_INVALID_ARGUMENT, *out_rows left alone, for a height, band_rows or
+ *      band_stride of 0, and when the count does not fit 32 bits (it is below height + band_rows,
+ *      so a height of at most FRM_MAX_DIMENSION always fits).
+ * frm_render_bands: dev_dst holds dst_bytes bytes, at least frm_band_rows_for's rows of 4*width
+ *      bytes (FRM_ERR_BUFFER_TOO_SMALL otherwise), and is 4-byte aligned; dev_counters, if not
+ *      NULL, is 8-byte aligned (FRM_ERR_INVALID_ARGUMENT otherwise, reported after every other
+ *      fault of the call; a refused call launches nothing). The rows a short last band lacks are
+ *      padding: they are never written and keep the caller's bytes, as does every byte outside the
+ *      call's rows. A call without bands (0 rows) succeeds with a dst_bytes of 0 and writes nothing. */
 #define FRM_NUM_COUNTERS 8u
 int frm_band_rows_for(uint32_t height, uint32_t band_rows, uint32_t first_band,
                       uint32_t band_stride, uint32_t* out_rows);
@@ -375,7 +386,11 @@ int frm_render_bands(frm_ctx* ctx, uint8_t* dev_dst, size_t dst_bytes, uint32_t 
  * fly-through (the CLI's, bench.py's HEADLINE_FLY) so renders several of its frames per launch. The context's parameters become params[count-1].
  * Counters are added over all frames. Bytes per frame are those of frm_render_bands; dev_dst
  * holds dst_bytes bytes, at least (count - 1) * frame_stride_bytes + one frame's bands
- * (FRM_ERR_BUFFER_TOO_SMALL otherwise); frame_stride_bytes is a multiple of 4 below 16 GiB. */
+ * (FRM_ERR_BUFFER_TOO_SMALL otherwise); frame_stride_bytes is a multiple of 4 below 16 GiB.
+ * dev_dst is 4-byte aligned and dev_counters, if not NULL, 8-byte aligned (FRM_ERR_INVALID_ARGUMENT
+ * otherwise, reported after every other fault of the call; a refused call launches nothing). As
+ * with frm_render_bands, the padding rows of a short last band are never written, nor are the
+ * bytes between one frame's rows and the next frame's start. */
 #define FRM_MAX_BATCH 32u
 int frm_render_bands_batch(frm_ctx* ctx, uint32_t count, const frm_parameters* params,
                            uint8_t* dev_dst, size_t dst_bytes, size_t frame_stride_bytes, uint32_t band_rows,
@@ -583,7 +598,18 @@ int frm_get_depth_of_field(const frm_ctx* ctx, float* out_aperture, float* out_f
 int frm_read_depth(frm_ctx* ctx, float* dst, size_t n_floats);
 /* Reassemble a frame from per-rank band buffers laid out rank-major in dev_src
  * (rank r's buffer starts at r*rank_stride_bytes, as written by frm_render_bands with
- * first_band = r, band_stride = ranks) into row-major dev_dst. Asynchronous. */
+ * first_band = r, band_stride = ranks) into row-major dev_dst. Asynchronous on `stream` (NULL:
+ * the context's). dev_dst holds dst_bytes bytes, at least the frame's 4*width*height
+ * (FRM_ERR_BUFFER_TOO_SMALL otherwise); rank_stride_bytes is a multiple of 4, at least rank 0's
+ * frm_band_rows_for rows of 4*width bytes. The call reads dev_src from its first byte to the end of
+ * the rows (whole bands) of the last rank that holds a band, rank min(ranks, band count) - 1, and
+ * of these only the rows that hold frame rows: padding rows, the bytes between a rank's rows and
+ * the next rank's start and the shares of ranks beyond the band count are never read. dev_src
+ * and dev_dst are device memory of the context's GPU, 4-byte aligned, and the frame at dev_dst
+ * does not overlap that span of dev_src (FRM_ERR_INVALID_ARGUMENT otherwise, reported after every
+ * other fault of the call; a refused call launches nothing). Rows move as 16-byte words when
+ * 4*width, rank_stride_bytes, dev_src and dev_dst are all multiples of 16, else as 4-byte words:
+ * the bytes are the same. */
 int frm_unshuffle_bands(frm_ctx* ctx, const uint8_t* dev_src, size_t rank_stride_bytes,
                         uint8_t* dev_dst, size_t dst_bytes, uint32_t band_rows,
                         uint32_t ranks, void* stream);
