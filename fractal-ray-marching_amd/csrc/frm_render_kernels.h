@@ -688,6 +688,21 @@ __device__ unsigned long long g_wave_debug[16u * kWaveDebugSlots];
 #ifndef FRM_COUNT_DOWN
 #define FRM_COUNT_DOWN 1  // 0: the body loop counts its bodies up and compares twice (A/B builds)
 #endif
+// The full service pass of the Mandelbulb launches (DESIGN.md section 5, round 12;
+// profiles/round12/pass). 0 everywhere is the earlier code, instruction for instruction; none of
+// them touches the ring grid or the fixed-trip families. All three are bit-exact and each takes
+// instructions out of the pass (-6, -9 and -3 VALU); on is what measured faster on the headline
+// step by step: the tap store alone -1.0 %, the masks alone +-0, the tap offsets alone +0.7 %
+// (slower), all three -1.0 % like the tap store alone, which is also ahead on the 8K and moving frames.
+#ifndef FRM_PASS_MASKS
+#define FRM_PASS_MASKS 0  // 1: "the DE has its result" as a wave-uniform mask instead of a per-lane flag (no gain alone)
+#endif
+#ifndef FRM_TAP_STORE
+#define FRM_TAP_STORE 1  // 1: the first three tap distances kept as they are, summed at the fourth tap
+#endif
+#ifndef FRM_TAP_OFFSET
+#define FRM_TAP_OFFSET 0  // 1: the start-DE block adds -0.0f for lanes that are no tap, no final selects (slower alone)
+#endif
 
 // The Mandelbulb body loop's counter (FRM_COUNT_DOWN): the bodies a lane's DE has left before its
 // count exit, N where the DE starts. One subtract-with-borrow per iteration takes 1 from every lane
@@ -797,6 +812,11 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
   // Not the ring grid (its register budget is fragile), nor the fixed-trip families.
   constexpr bool kLeanPass = FRM_LEAN_PASS && kMb && !RES;
   constexpr bool kCountDown = FRM_COUNT_DOWN && kMb;  // count_down() above; else `body` counts up
+  // Round 12, the launches of the lean pass (whose masks they use): the per-lane `done` flag as
+  // the mask done_m; tap distances stored, not summed; tap offsets without their final selects
+  constexpr bool kPassMasks = FRM_PASS_MASKS && kLeanPass;
+  constexpr bool kTapStore = FRM_TAP_STORE && kMb && !RES;
+  constexpr bool kTapOffset = FRM_TAP_OFFSET && kMb && !RES;
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
   const uint64_t lane_bit = 1ull << lane;
   constexpr bool multi = MULTI;
@@ -867,6 +887,10 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
   uint32_t pix = kIdle;      // local pixel index (lr * width + x) being marched
   uint32_t phase = kPrimary;
   bool done = false;         // the current DE has its result
+  // kPassMasks: the same set as a wave-uniform mask (SGPRs), in place of `done`. As a flag it was
+  // set under one branch and read under another, so each crossing widened it to 0/1 in a VGPR and
+  // compared it back into a mask. Bits of lanes without a pixel mean nothing (masked by `live`).
+  [[maybe_unused]] uint64_t done_m = 0;
   v3 o = mk(0.f, 0.f, 0.f), d = o, nsum = o, q = o, z = o;
   float t = 0.f, closeness = 0.f, dr = 1.f, mag = 0.f, de = 0.f;
   uint32_t it = 0, psteps = 0, body = 0;
@@ -896,7 +920,7 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
       // body directly (inverse ballot -> exec) and one ballot per iteration retires lanes,
       // instead of a per-lane flag merged under exec masks every iteration.
       const uint64_t live = ballot(pix != kIdle);
-      uint64_t pending = live & ~ballot(done);
+      uint64_t pending = live & ~(kPassMasks ? done_m : ballot(done));
       // lanes that count as waiting when not pending: finished DEs, and idle lanes while
       // the queue still has pixels
       const uint64_t waitable = exhausted ? live : ~0ull;
@@ -936,7 +960,7 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
         else
           pending &= ~(ballot(body > n_iter) | ballot(mag > su.mb_bailout));
       }
-      done = !lane_in(pending);  // idle lanes: masked by cons
+      if constexpr (!kPassMasks) done = !lane_in(pending);  // idle lanes: masked by cons
       live_m = live;
       cons_m = live & ~pending;
     }
@@ -948,14 +972,26 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
     // 1. consume finished DEs. Branch-light: the bookkeeping of every phase is computed for
     //    every lane with selects; only the distance, the last-tap transition (normal, record,
     //    shadow ray) and the record store of a finished pixel are branches.
-    const bool cons = pix != kIdle && done;
+    // (kPassMasks: the consuming lanes are the body loop's mask, live & ~pending)
+    const bool cons = kPassMasks ? lane_in(cons_m) : (pix != kIdle && done);
     bool ev_bail = false;
+    if constexpr (kPassMasks) {
+      // DEs that left by bailout (before the first body included), counted from the mask of one
+      // compare by every lane: a flag set under `if (cons)` reached the count through a VGPR
+      const uint64_t in_count = kCountDown ? ballot(left <= n_iter) : ballot(body <= n_iter);
+      n_bail.add((uint32_t)__popcll(cons_m & in_count));
+    }
     // the distance's log without its special-value selects (and with the integer exponent
     // split) when every consuming lane's magnitude is positive, normal and finite
     // (wave-uniform test; same bits)
     bool plain_log = true;
-    if constexpr (kMb && !kHw)
-      plain_log = ballot(cons && !__builtin_amdgcn_classf(mag, 0x100 /* +normal */)) == 0;
+    if constexpr (kMb && !kHw) {
+      if constexpr (kPassMasks)  // the same class as an integer range of the bits, [2^-126, inf): the ballot of a
+                                 // class test is widened to 0/1 and compared again, a compare's is its mask
+        plain_log = (cons_m & ballot(__float_as_uint(mag) - 0x00800000u >= 0x7F000000u)) == 0;
+      else
+        plain_log = ballot(cons && !__builtin_amdgcn_classf(mag, 0x100 /* +normal */)) == 0;
+    }
     if (cons) {
       done = false;
       if constexpr (kMb) {
@@ -1034,19 +1070,30 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
     need_point = ev_hit || (step && more) || tap;  // start a DE at the phase's next sample point
     // tap k adds s_k * d to the sum (k = 0 sets it); s_0..s_3 = (+--), (--+), (-+-), (+++)
     const uint32_t k = phase - kTap0;
+    if constexpr (kTapStore) {
+      // The sums are read at the fourth tap only, so until then nsum's registers hold the first
+      // three taps' distances as they come (one select each; 4 % of the consumed DEs are taps)
+      // and the fourth-tap branch below adds them up.
+      nsum = mk((cons && k == 0u) ? de : nsum.x, (cons && k == 1u) ? de : nsum.y, (cons && k == 2u) ? de : nsum.z);
+    } else {
     const float dx = (k == 0u || k == 3u) ? de : -de, dy = (k >= 2u) ? de : -de,
                 dz = (k == 1u || k == 3u) ? de : -de;
     // (component-wise: a select of whole structs compiles to a select of stack addresses)
     const float sx = (k == 0u) ? dx : nsum.x + dx, sy = (k == 0u) ? dy : nsum.y + dy,
                 sz = (k == 0u) ? dz : nsum.z + dz;
     nsum = mk(tap ? sx : nsum.x, tap ? sy : nsum.y, tap ? sz : nsum.z);
+    }
     phase = ev_hit ? kTap0 : (tap ? phase + 1u : phase);  // after the last tap: kShadow
     if (tap && k == kTap3 - kTap0) {  // normal, then the shadow ray toward the sun
       FRM_SUB_BEGIN();
+      // kTapStore: the same f32 additions in the same order as the running sums (tap 0 sets the
+      // sum, taps 1..3 add s_k * d; a negation is exact)
+      const float d0 = nsum.x, d1 = nsum.y, d2 = nsum.z;
+      const v3 ns = kTapStore ? mk(((d0 + -d1) + -d2) + de, ((-d0 + -d1) + d2) + de, ((-d0 + d1) + -d2) + de) : nsum;
 #if defined(__HIP_DEVICE_COMPILE__)  // one reciprocal for the three quotients when the lanes allow it (same bits)
-      const v3 n = normalize_wave(nsum);
+      const v3 n = normalize_wave(ns);
 #else
-      const v3 n = normalize(nsum);
+      const v3 n = normalize(ns);
 #endif
       const v3 hp = ray_at(o, t, d);
       if constexpr (RES) {  // read by another wave's shading, maybe on another XCD (ring_flush)
@@ -1076,7 +1123,7 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
       FRM_SUB_END(3);
     }
     }  // !lean
-    if constexpr (kLeanPass) n_bail.add((uint32_t)count(ev_bail));
+    if constexpr (kLeanPass && !kPassMasks) n_bail.add((uint32_t)count(ev_bail));
     if constexpr (RES) {  // drained slots whose last pixels left the lanes
       const uint32_t gone = rw_get(rw, kRwGone);
       if (gone) ring_settle(ring_lds, rw, gone, pix);
@@ -1247,6 +1294,17 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
 #endif
       if (no_tap) {
         q = r;
+      } else if constexpr (kTapOffset) {
+        // The same point without the three final selects: a lane that is no tap adds -0.0f, which
+        // leaves every x its bits (both zeros included; a NaN stays a NaN). A tap adds
+        // +-MIN_DISTANCE with the sign bit looked up by the phase in a six-entry bit table
+        // (entries 0 and 5, the march phases, are the -0.0f's sign): a shift and a v_lshl_or each
+        // instead of the compare pairs. x is negative for taps 1 and 2, y for 0 and 1, z for 0 and 2.
+        const bool is_tap = phase - kTap0 <= kTap3 - kTap0;
+        const uint32_t e = is_tap ? __float_as_uint(kMinDistance) : 0u;
+        constexpr uint32_t kNegX = 0x2Du, kNegY = 0x27u, kNegZ = 0x2Bu;  // bit `phase`: the offset is negative
+        q = mk(r.x + __uint_as_float(((kNegX >> phase) << 31) | e), r.y + __uint_as_float(((kNegY >> phase) << 31) | e),
+               r.z + __uint_as_float(((kNegZ >> phase) << 31) | e));
       } else {
         // normal tap k samples r + s_k * MIN_DISTANCE (normal_tap_pos), with selects
         const uint32_t kq = phase - kTap0;
@@ -1263,7 +1321,7 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
         else
           body = 0;
         mag = mb_length<kHw>(q);
-        done = mag > su.mb_bailout;
+        if constexpr (!kPassMasks) done = mag > su.mb_bailout;
       } else {
         DeCount unused = {0u, 0u};
         de = scene_de<FAM, ITERS>(su, q, unused);
@@ -1271,6 +1329,13 @@ __global__ __launch_bounds__(kMarchBlock, RES ? FRM_RING_WAVES_PER_SIMD : FRM_MA
         pix_cost++;  // fixed-trip families: the scheduling cost unit is one DE
       }
     }
+    // kPassMasks: the DEs that bailed out at entry, one compare by every lane outside the branch
+    // (a mask assigned inside it joins the other path's through a VGPR, and so does one combined
+    // with need_point). The other lanes need no masking: a lane that holds a pixel here and did
+    // not start a DE was still pending when the body loop left, so its magnitude is not above the
+    // bailout (the loop retires such a lane at once), and a consumed lane either started a DE or
+    // gave up its pixel.
+    if constexpr (kPassMasks) done_m = ballot(mag > su.mb_bailout);
 
     // work counters (frm_stats); a ring grid's frames report none (frm_render with stats renders
     // outside the ring), so it keeps no counters

@@ -6,6 +6,9 @@ opcodes it did not measure are priced by the class they resemble and marked '~')
 usage: python tools/isa_histogram.py build/frm_kernels.s [KERNEL_SUBSTRING]
 
 Blocks of the Mandelbulb kernel (found from the structure the compiler emits):
+  full pass    one full service pass on its common path, walked branch by branch (the rules are
+               common_full_pass's; every branch decision is printed), with the outer loop's top
+  lean pass    the same walk through the lean path
   tame test    the inner loop's head up to the branch into the exact body
   tame body    the fast-path body (frm_fast.h) up to the join with the exact body
   loop tail    body count, magnitude (the common sqrt_nosmall path), bailout test, back edge
@@ -98,10 +101,97 @@ def report(name, c):
         print(f"   {op:28s} {n:4d} x {p:5.2f}{mark:1s} = {p * n:6.1f}")
 
 
+def is_op(line, prefix):
+    s = line.strip()
+    return bool(s) and s.split()[0].startswith(prefix)
+
+
+def common_full_pass(L, start, end, lean=False):
+    """The instructions of one full service pass on its common path, walked from the body loop's
+    exit (line `start`) to the outer loop's back edge (line `end`) by these rules (lean: of one
+    lean pass, which takes the wave-uniform branch over the full path, more than 100 lines):
+      * a branch to a block behind the outer back edge (the counters' carry blocks) is not taken;
+      * a divergent region (s_and_saveexec + s_cbranch_execz) is skipped when it stores to global
+        memory or claims from the queue (the fourth tap's normal and record, a finished pixel's
+        record: the rare events), and entered otherwise (the distance, the start-DE block);
+      * a wave-uniform forward branch is taken when the code it jumps over is one special-value
+        block (under 48 lines with the log's v_frexp_mant or the square root's 2^32 rescale), and falls
+        through otherwise: the full path rather than the lean one, no refill, the tap offsets.
+    -> (lines walked, [(line number, branch, 'taken' | 'not taken')])"""
+    labels = {l.split(":")[0]: i for i, l in enumerate(L) if l.startswith(".LBB")}
+    out, trace, i, steps = [], [], start, 0
+    while i < end and steps < 10 * len(L):
+        steps += 1
+        s = L[i].strip()
+        op = s.split()[0] if s else ""
+        if op == "s_branch":
+            t = labels.get(s.split()[-1], end)
+            trace.append((i, s, "taken"))
+            if t <= i:
+                break
+            i = t
+            continue
+        if op.startswith("s_cbranch"):
+            t = labels.get(s.split()[-1], end)
+            if t <= i:  # a loop of the refill, or the outer back edge
+                break
+            jumped = L[i + 1:t]
+            if t > end:
+                take = False
+            elif op == "s_cbranch_execz":
+                take = any(is_op(l, ("global_store", "global_atomic")) for l in jumped)
+            elif op == "s_cbranch_execnz":
+                take = True
+            elif lean and len(jumped) > 100 and not any(is_op(l, "global_atomic") for l in jumped):
+                take = True
+            elif lean and len(jumped) < 24 and any(is_op(l, "v_add_f32") for l in jumped) and not any(
+                    is_op(l, ("s_cbranch", "s_branch", "s_and_saveexec")) for l in jumped):
+                take = True  # no lane is a tap: the start-DE block's tap offsets are jumped over
+            else:
+                take = len(jumped) < 48 and any("v_frexp_mant" in l or "0x4f800000" in l for l in jumped)
+            trace.append((i, s, "taken" if take else "not taken"))
+            out.append(L[i])
+            i = t if take else i + 1
+            continue
+        out.append(L[i])
+        i += 1
+    return out, trace
+
+
+def report_full_pass(L, want):
+    """The "full pass, common path" count; needs only the body loop's header and the two back edges."""
+    head = next(i for i, l in enumerate(L) if "Inner Loop Header" in l)
+    while not L[head].startswith(".LBB"):
+        head -= 1
+    name = L[head].split(":")[0]
+    back = next(i for i in range(head, len(L)) if re.search(r"s_cbranch_\w+ " + re.escape(name) + r"$", L[i]))
+    first = next(i for i, l in enumerate(L) if l.startswith(".LBB"))
+    # the outer back edge: the last backward branch to a label in front of the body loop
+    labels = {l.split(":")[0]: i for i, l in enumerate(L) if l.startswith(".LBB")}
+    outer = max(i for i in range(back, len(L)) if re.match(r"\s*s_cbranch_\w+ \.LBB", L[i])
+                and first <= labels.get(L[i].split()[-1], len(L)) < head)
+    # the outer loop's top, up to the body loop's header, belongs to the pass
+    top = labels[L[outer].split()[-1]]
+    top_lines, _ = common_full_pass(L, top, head)
+    for name, lean in (("full pass, common path", False), ("lean pass", True)):
+        lines, trace = common_full_pass(L, back + 1, outer + 1, lean)
+        report(f"{name} (kernel lines {back + 1} .. {outer}, and the loop's top {top} .. {head})", hist(lines + top_lines))
+        for i, s, what in trace:
+            print(f"   line {i:5d}  {s:40s} {what}")
+
+
 def main():
     path = sys.argv[1]
     want = sys.argv[2] if len(sys.argv) > 2 else "march_persistentILj3ELb1ELb1E"
     L = kernel_lines(path, want)
+    report_full_pass(L, want)
+    try:
+        loop_blocks(L, want)
+    except (StopIteration, IndexError):
+        print("(body-loop blocks: the listing's layout is not the one this tool knows; see tools/asm_loops.py)")
+
+
+def loop_blocks(L, want):
     head = next(i for i, l in enumerate(L) if "Inner Loop Header: Depth=2" in l)
     while not L[head].startswith(".LBB"):
         head -= 1  # the header comment follows its label
