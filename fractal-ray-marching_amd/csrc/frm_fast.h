@@ -208,7 +208,8 @@ __device__ __forceinline__ float atan2_tame(float y, float x) { return atan2_tam
 // body's operands once mb_tame() has admitted the wave: it sends zero components to the exact
 // body). The sign of x is then x's own sign bit: no -0 to turn into +0 first, one add less. The
 // rest is atan2_tame's, operation for operation (the 2^-100 floor of mx never applies here).
-// mb_body_tame takes it with -DFRM_ATAN2_NZ=1 only: the headline measured slower with it.
+// mb_body_tame does not take it: the headline measured slower with it (DESIGN.md section 6,
+// profiles/round11/loop/atan2_nz.patch). Kept for that patch, and pinned by the math tests.
 __device__ __forceinline__ float atan2_tame_nz(float y, float x) { return atan2_tame_<true>(y, x); }
 
 // log_split_ for positive normal finite x by integer arithmetic (the musl logf split):

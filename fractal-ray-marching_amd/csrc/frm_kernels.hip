@@ -296,7 +296,7 @@ static hipError_t launch_family(const KernelArgs& args, KernelKind kind, int cu_
 
 // A resident ring grid (frm_ring.hip ring_launch): the occupancy limit of the RES instantiation
 // (the Mandelbulb's with per-lane powers: ring frames differ in time) over every CU, the first
-// args.ring.service_waves workgroups serving the ring (frm_render_kernels.h ring_service).
+// args.ring.service_waves workgroups serving the ring (frm_ring_kernels.h ring_service).
 template <uint32_t FAM, bool ITERS>
 static hipError_t launch_ring_fam(const KernelArgs& args, int cu_count, hipStream_t stream, int* out_blocks) {
   constexpr bool kAnim = is_mandelbulb(FAM);

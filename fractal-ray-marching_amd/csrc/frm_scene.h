@@ -334,16 +334,11 @@ __device__ __forceinline__ bool mb_tame(v3 z, float r) {
 }
 
 // mb_body (frm_scene.h) with the tame primitives: the same operations in the same order.
-#ifndef FRM_ATAN2_NZ
-#define FRM_ATAN2_NZ 0  // 1: atan2_tame_nz, one add less (slower, alone and with the others: DESIGN.md section 6)
-#endif
-#ifndef FRM_ER_SIGN_OR
-#define FRM_ER_SIGN_OR 1  // 0: the z sign onto er by xor, a shift and an xor (A/B builds)
-#endif
 __device__ __forceinline__ void mb_body_tame(float P, float Pm1, v3 c, float r, v3& z, float& dr) {
   float theta = acos_dev(div_tame_nz(z.z, r));  // acos_dev(-0) == acos_dev(+0)
-  // (mb_tame: |z.x|, |z.y| >= 2^-60, neither is a zero, which is all atan2_tame_nz needs)
-  float phi = FRM_ATAN2_NZ ? atan2_tame_nz(z.y, z.x) : atan2_tame(z.y, z.x);
+  // (mb_tame: |z.x|, |z.y| >= 2^-60, neither is a zero, which is all atan2_tame_nz would need; it
+  // is one add less and measured slower: DESIGN.md section 6, profiles/round11/loop/atan2_nz.patch)
+  float phi = atan2_tame(z.y, z.x);
   float l2 = log2_tame(r);
   const float pm1 = exp2_tame(Pm1 * l2);
   dr = fma_(pm1 * P, dr, 1.0f);
@@ -359,11 +354,7 @@ __device__ __forceinline__ void mb_body_tame(float P, float Pm1, v3 c, float r, 
   const float er_xy = __uint_as_float(__float_as_uint(er) ^ ((tt + tp) << 31));
   // er is positive (a product of the positive normal pm1 and r: >= 2^-117, mb_tame above), its
   // sign bit clear, so or-ing the sign in equals the xor: one v_lshl_or_b32
-#if FRM_ER_SIGN_OR
   const float er_z = __uint_as_float(__float_as_uint(er) | (tt << 31));
-#else
-  const float er_z = __uint_as_float(__float_as_uint(er) ^ (tt << 31));
-#endif
   z = mk(fma_(er_xy, st * cp, c.x), fma_(er_xy, sp * st, c.y), fma_(er_z, ct, c.z));
 }
 

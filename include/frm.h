@@ -639,7 +639,7 @@ enum {
   FRM_MATH_DIV_FIX = 21, FRM_MATH_NORMALIZE_GUARDED_X = 22, FRM_MATH_NORMALIZE_GUARDED_Y = 23,
   FRM_MATH_NORMALIZE_X = 24, FRM_MATH_NORMALIZE_Y = 25,
   /* atan2_tame for two non-zero operands (csrc/frm_fast.h atan2_tame_nz; the Mandelbulb body's
-     with -DFRM_ATAN2_NZ=1) */
+     with profiles/round11/loop/atan2_nz.patch) */
   FRM_MATH_ATAN2_TAME_NZ = 26,
   FRM_MATH_LAST = 26
 };

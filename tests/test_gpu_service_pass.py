@@ -1,5 +1,5 @@
 """The persistent march kernel's full service pass after round 12 (frm_render_kernels.h
-FRM_PASS_MASKS, FRM_TAP_STORE, FRM_TAP_OFFSET): passes in which refilling, primary, tap and shadow
+FRM_PASS_MASKS, kTapStore, FRM_TAP_OFFSET): passes in which refilling, primary, tap and shadow
 lanes meet. FRM_BLOCKS_PER_CU=1 (read at every launch) leaves one wave per CU, so a frame of
 3 x 64 x CU-count pixels gives every wave several chunks: its lanes hold pixels in every phase while
 others refill. Bytes and the seven work counters must equal the live oracle's over three launches

@@ -1,5 +1,5 @@
 """The two float32 identities the persistent march kernel's full service pass relies on
-(frm_render_kernels.h FRM_TAP_OFFSET, FRM_TAP_STORE), checked bit for bit in numpy float32:
+(frm_render_kernels.h FRM_TAP_OFFSET, kTapStore), checked bit for bit in numpy float32:
 
 * x + (-0.0) has the bits of x for every x that is not a NaN, both zeros and the denormals
   included, and a NaN stays a NaN: a lane that is no normal tap may add -0.0f to its sample point
