@@ -141,6 +141,13 @@ FRM_HD float atan2_(float y, float x) {
   float r = fma_(a * s, atan_poly(s), a);
   r = (ay > ax) ? kHalfPi - r : r;
   r = (x < 0.0f) ? kPi - r : r;
+#if defined(__HIP_DEVICE_COMPILE__)
+  // |x| and |y| reach min_ / max_ without passing through arithmetic. IEEE minNum / maxNum (and
+  // the C library's fminf / fmaxf) answer a signalling NaN with a NaN and drop only a quiet one;
+  // the device's fminf / fmaxf quiet their operands first and drop both kinds. Computed operands
+  // are never signalling, so only a raw one (frm_eval_math) can tell.
+  r = (__builtin_amdgcn_classf(x, 0x001 /* signalling NaN */) || __builtin_amdgcn_classf(y, 0x001)) ? __builtin_nanf("") : r;
+#endif
   return copysignf(r, y);
 }
 

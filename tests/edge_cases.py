@@ -141,6 +141,38 @@ for _scene in (0, 4, 12):
 CASES.append(EdgeCase("sierpinski_n31", 15, 31, 0.5, P1, 40, 24, 100, ("de_zero", "primary_end_hit", "shadow_end_hit")))
 CASES.append(EdgeCase("sierpinski_n33", 15, 33, 0.5, P1, 40, 24, 100, ("primary_end_far",)))
 
+# Extreme cameras: nothing refuses a subnormal, far, infinite or NaN camera position, so these are
+# legal frames. The far cameras end every ray at step 0 (distance over MAX_TOTAL_DISTANCE; Koch's
+# folds overflow to inf - inf = NaN at 3e38). The subnormal, inf and NaN cameras do not: minNum /
+# maxNum drop a NaN or inf coordinate in Menger's box and folds, so scene 0 still hits pixels and
+# marches shadow rays; Sierpinski and Koch give NaN distances; the Mandelbulb's atan2 of two
+# subnormals (max below 2^-128: RN(1 / max) = inf) is NaN, and so is every body of the inf and
+# NaN cameras, which run all N + 1 bodies per pixel without a bailout.
+CAMERA_POSITIONS = (
+    ("sub", (1e-40, -1e-42, -2.0)), ("far_1e4", (0.0, 0.0, -1e4)), ("far_oblique", (3e3, 2e3, -1e4)),
+    ("far_1e19", (0.0, 0.0, -1e19)), ("far_3e38", (1e30, 0.0, -3e38)), ("inf", (float("inf"), 0.0, -1.0)),
+    ("nan", (float("nan"), 0.0, -2.0)))
+CAMERA_SCENES = ((0, 3, 1.0), (15, 3, 1.0), (16, 3, 1.0), (18, 6, P8))  # (scene, N, time)
+_CAM_HITS = (("primary_end_hit", "primary_end_far", "shadow_divs"), ("primary_end_nan",))
+_CAM_FAR = (("primary_end_far",), ("primary_end_hit", "primary_end_nan", "primary_end_steps", "shadow_divs"))
+_CAM_NAN = (("primary_end_nan", "primary_t0_dnan"), ("primary_end_hit", "primary_end_far", "primary_end_steps", "shadow_divs"))
+
+
+def _camera_events(scene, tag):
+    if tag.startswith("far"):
+        return _CAM_NAN if (scene, tag) == (16, "far_3e38") else _CAM_FAR
+    if scene == 0 or tag == "sub" and scene != 18:
+        return _CAM_HITS
+    return (_CAM_NAN[0] + ("mb_de_nan", "mb_dr_nan"), _CAM_NAN[1]) if scene == 18 else _CAM_NAN
+
+
+CAMERA_CASES = []
+for _scene, _n, _time in CAMERA_SCENES:
+    for _tag, _pos in CAMERA_POSITIONS:
+        _ev, _absent = _camera_events(_scene, _tag)
+        CAMERA_CASES.append(EdgeCase(f"cam{_scene}_{_tag}", _scene, _n, _time, (_pos, 0.0, 0.0), 33, 19, 64, _ev, _absent))
+CASES += CAMERA_CASES
+
 CASE_IDS = [c.name for c in CASES]
 MANDELBULB_CASES = [c for c in CASES if c.mandelbulb]
 
@@ -159,6 +191,11 @@ def reference(oracle, case):
         _REFS[case.name] = oracle.render(case.params(), case.width, case.height, case.max_steps, trace=True,
                                          census=True)
     return _REFS[case.name]
+
+
+def camera_batch_params(scene=0):
+    """The seven extreme cameras of one scene as the frames of one batch launch."""
+    return [c.params() for c in CAMERA_CASES if c.scene == scene]
 
 
 def mixed_params(time, width, height, iters=12):

@@ -29,6 +29,24 @@ def test_frame_case_host_replay_equals_oracle(host_replay, oracle, case):
     assert np.array_equal(c, ref["counters"])
 
 
+def test_extreme_cameras_do_what_they_are_for(oracle):
+    """From the oracle alone: on scene 0 the subnormal, inf and NaN cameras each hit at least one
+    pixel and march shadow rays; every far camera of every scene ends each ray after its one step
+    at t = 0; the inf and NaN cameras run all N + 1 Mandelbulb bodies per pixel without a bailout."""
+    assert len(ec.CAMERA_CASES) == 28 and all(c.camera[1:] == (0.0, 0.0) for c in ec.CAMERA_CASES)
+    for case in ec.CAMERA_CASES:
+        pixels, hits, primary, shadow, _, bodies, bailouts = (int(v) for v in ec.reference(oracle, case)["counters"][:7])
+        tag = case.name.split("_", 1)[1]
+        print(case.name, pixels, hits, primary, shadow, bodies, bailouts)
+        assert pixels == case.width * case.height == 627
+        if case.scene == 0 and not tag.startswith("far"):
+            assert hits >= 1 and shadow >= 1, case.name
+        if tag.startswith("far"):
+            assert hits == 0 and shadow == 0 and primary == pixels, case.name
+        if case.scene == 18 and tag in ("inf", "nan"):
+            assert bodies == pixels * (case.iters + 1) and bailouts == 0, case.name
+
+
 def test_census_changes_no_output_and_is_thread_independent(oracle):
     case = ec.CASES[ec.CASE_IDS.index("mb_inside")]
     p = case.params()

@@ -1,7 +1,8 @@
 """GPU parity at the numerically delicate inputs of tests/edge_cases.py: degenerate cameras
 (NaN, -inf and 0 / 0 closeness, r < 2^-13 at every body), the Mandelbulb power's two ends, deep
 points whose dr passes 2^125 or overflows, Koch and Menger at the iteration counts where their
-scales overflow or their distances go subnormal. tests/test_edge_census.py proves on the CPU,
+scales overflow or their distances go subnormal, and subnormal, far, infinite and NaN camera
+positions on four scenes. tests/test_edge_census.py proves on the CPU,
 from the oracle's census alone, that every case reaches the events it is named for; here both
 march kernels must equal the oracle on them, bytes, work counters and (Mandelbulb) traces."""
 import math
@@ -118,6 +119,37 @@ def test_mixed_waves_in_one_batch_launch(frm_lib, oracle, time, iters):
             for k, ref in enumerate(refs):
                 diff = np.any(img[k] != ref["rgba"], axis=-1)
                 assert not diff.any(), f"launch {launch} frame {k}: {diff.sum()} pixels differ"
+            got = [int(v) for v in counters.cpu().tolist()][:7]
+            assert got == [sum(int(ref["counters"][i]) for ref in refs) for i in range(7)], f"launch {launch}"
+
+
+def test_extreme_cameras_in_one_batch_launch(frm_lib, oracle):
+    """The seven extreme cameras of scene 0 (subnormal, four far ones, inf, NaN) as the frames of
+    one frm_render_bands_batch launch: the far frames' rays all end at step 0 beside the inf
+    camera's, whose pixels march 18,304 shadow steps with an infinite origin. Each frame equals the
+    oracle's bytes and the launch's counters the frames' sums, over two launches."""
+    import torch
+
+    cases = [c for c in ec.CAMERA_CASES if c.scene == 0]
+    assert len(cases) == 7
+    w, h, steps = cases[0].width, cases[0].height, cases[0].max_steps
+    ps = ec.camera_batch_params(0)
+    refs = [ec.reference(oracle, c) for c in cases]
+    fb = w * h * 4
+    out = torch.zeros(len(ps) * fb, dtype=torch.uint8, device="cuda")
+    counters = torch.zeros(8, dtype=torch.int64, device="cuda")
+    with frm.Renderer(device=0, max_steps=steps, flags=frm.FRM_FLAG_PERSISTENT_KERNEL) as r:
+        r.resize(w, h)
+        for launch in range(2):
+            counters.zero_()
+            out.zero_()
+            r.render_bands_batch(ps, out.data_ptr(), dst_bytes=out.numel(), frame_stride=fb, band_rows=h, first_band=0,
+                                 band_stride=1, stream=0, dev_counters=counters.data_ptr())
+            torch.cuda.synchronize()
+            img = out.cpu().numpy().reshape(len(ps), h, w, 4)
+            for c, ref in zip(cases, refs):
+                diff = np.any(img[cases.index(c)] != ref["rgba"], axis=-1)
+                assert not diff.any(), f"launch {launch} {c.name}: {diff.sum()} pixels differ"
             got = [int(v) for v in counters.cpu().tolist()][:7]
             assert got == [sum(int(ref["counters"][i]) for ref in refs) for i in range(7)], f"launch {launch}"
 
