@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import frm
+import ring_cases
 from helpers import params_for
 
 pytestmark = pytest.mark.gpu
@@ -58,22 +59,32 @@ def _check(oracle, frames, got, w=W, h=H, steps=256):
 
 @pytest.mark.parametrize("fif", [2, 3])
 @pytest.mark.parametrize("lag", [0, 1])
-def test_ring_moving_loop_bit_exact(frm_lib, oracle, fif, lag):
+def test_ring_moving_loop_bit_exact(frm_lib, oracle, monkeypatch, capfd, fif, lag):
+    monkeypatch.setenv("FRM_RING_DEBUG", "1")  # the totals line of ring_destroy: the ring served every frame
     frames = _moving(9)
-    with frm.Renderer(device=0, max_steps=256, flags=PERSISTENT, frames_in_flight=fif) as r:
+    r = frm.Renderer(device=0, max_steps=256, flags=PERSISTENT, frames_in_flight=fif)
+    try:
         r.resize(W, H)
         got = _loop(r, frames, lag)
+    finally:
+        posted, _ = ring_cases.close_and_count(r, capfd)
     _check(oracle, frames, got)
+    assert posted == sum(ring_cases.eligible(256, 8, pixels=W * H, frames_in_flight=fif) for _ in frames) == 9
 
 
 @pytest.mark.parametrize("scene,iters", [(0, 4), (15, 5), (16, 3), (13, 3), (18, 0)])
-def test_ring_families_bit_exact(frm_lib, oracle, scene, iters):
+def test_ring_families_bit_exact(frm_lib, oracle, monkeypatch, capfd, scene, iters):
     # fixed pose, the other families (animated Menger scene 13 at a fixed time), N = 0 Mandelbulb
+    monkeypatch.setenv("FRM_RING_DEBUG", "1")
     frames = [params_for(scene, iters, 1.25, W, H, pose=pose) for pose in ("P1", "P1", "P2", "P0")]
-    with frm.Renderer(device=0, max_steps=256, flags=PERSISTENT, frames_in_flight=2) as r:
+    r = frm.Renderer(device=0, max_steps=256, flags=PERSISTENT, frames_in_flight=2)
+    try:
         r.resize(W, H)
         got = _loop(r, frames, 1)
+    finally:
+        posted, _ = ring_cases.close_and_count(r, capfd)
     _check(oracle, frames, got)
+    assert posted == sum(ring_cases.eligible(256, iters, pixels=W * H, frames_in_flight=2) for _ in frames) == 4
 
 
 def test_ring_sphere_extension(frm_lib, oracle):
